@@ -1,6 +1,6 @@
 """bench.py — env-steps/s of beergame-v0 at 65,536 envs per GPU (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one BeerGameVecEnv.step() over this rank's 65,536 envs: one fused HIP step
@@ -11,6 +11,10 @@ synthetic uniform integers in [0, 8], generated on device before timing (the pol
 output, resident in HBM). Envs shard across ranks by global id; the only collective is the
 async RCCL all-gather of per-env episode returns at each episode end.
 
+A plain run sets up, warms up, times the K steps and prints the line with the headline
+(`value`, `ms_per_step`). --dump-outputs DIR then writes what the last timed step returned
+(dump_outputs). Everything below from `headline_split` on runs and is reported with --full only.
+
 Timing (rank 0 prints ONE JSON line):
   * warm-up: max(W, 35) untimed steps — at least one whole 35-week episode, so every week
     kind of the plan and the auto-reset have run before timing — then one untimed region of
@@ -19,7 +23,8 @@ Timing (rank 0 prints ONE JSON line):
   * the timed region is exactly K steps, bracketed by barrier + synchronize, max over
     ranks; `value` = envs of all ranks x K / that wall time. Nothing inside is stamped
     (stamping the first and last launch cost a K = 20 region 0.3-0.6 us per step,
-    profiles/r02s_stamped_headline_ab.log); `headline_split` says what bounds it: the host's
+    profiles/r02s_stamped_headline_ab.log);
+  * --full from here on. `headline_split` says what bounds the headline: the host's
     enqueue time per step (the loop's wall time up to the final synchronize / K), the wait
     after it, the same brackets around zero steps (the region's fixed cost) and the GPU
     time per step of the 100-episode region below;
@@ -34,7 +39,9 @@ Timing (rank 0 prints ONE JSON line):
     kernel at 1,048,576 envs (272 MB per step, past the 256 MiB Infinity Cache);
   * `cpu_baseline` (rank 0, N = 1): oracle.beergame.BeerGameOracle — the per-env NumPy
     restatement of the reference step(), calibrated against the reference by
-    tools/cpu_calibration.py — on the host's cores.
+    tools/cpu_calibration.py — on the host's cores;
+  * `allgather_ok`: the last episode end's all-gather checked against every rank's own
+    returns (a mismatch exits non-zero).
 """
 import argparse
 import json
@@ -55,6 +62,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md chip table)
 EPISODES_TIMED = 100   # >= 100 episodes timed
 KERNEL = "bg_step_slab_kernel<4, 2>"
 BEYOND_CACHE_ENVS = 1 << 20
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
 
 
 def step_bytes_per_env(plan_word, week, T, L, ring_initial_slots, ledgers, history, returns, autoreset):
@@ -289,19 +297,23 @@ class StepLoop:
     def __init__(self, env, week_actions, gather=None):
         self.env, self.week_actions, self.gather = env, week_actions, gather
         self.episodes = 0
+        self.last = None  # what the latest plain step() call returned
 
     def run(self, k, first=None, last=None, each=None, sync_each=None):
         env, acts = self.env, self.week_actions
         if first is None and last is None and each is None and sync_each is None:
             step, gather, T = env.step, self.gather, len(acts)
             w = env.week
+            out = self.last
             for _ in range(k):  # the timed path: one action row and one step call per week
-                info = step(acts[w])[3]
+                out = step(acts[w])
+                info = out[3]
                 w = w + 1 if w + 1 < T else 0
                 if info:
                     self.episodes += 1
                     if gather is not None:
                         gather.on_episode_end(info["episode_return"])
+            self.last = out
             return
         for i in range(k):
             stamp = each[i] if each is not None else ((first, None) if i == 0 and first else None)
@@ -419,12 +431,46 @@ def beyond_cache_point(device, n_envs=BEYOND_CACHE_ENVS, episodes=2):
             "env_steps_per_s_gpu": n_envs * k / (ms / 1e3)}
 
 
+def snapshot_outputs(step_out, gathered):
+    """Host copies (float64 NumPy arrays, by name) of what a step() call returned, (obs,
+    reward, done, info) with info's tensors under their keys, plus the episode returns the
+    latest episode end handed on (`gathered`). Views of the env's output buffers are
+    copied here, before a later step overwrites them; a part that is None is left out."""
+    import numpy as np
+    obs, rew, done, info = step_out
+    named = {"obs": obs, "reward": rew, "done": done, "episode_return_gathered": gathered}
+    named.update({f"info_{k}": v for k, v in sorted((info or {}).items())})
+    return {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64)
+            for k, v in named.items() if v is not None}
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """Write `arrays` as DIR/<name>.npy (DIR/<name>_rank<r>.npy on several ranks), float64.
+    Past DUMP_MAX_BYTES in all, every array keeps the same fraction of its rows (first axis),
+    drawn with a generator seeded alike for each, so arrays of one row count keep the same
+    rows, in order."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES and a.ndim and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (DUMP_MAX_BYTES / total) * 0.99))
+            a = a[np.sort(np.random.RandomState(SEED).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3500)
     ap.add_argument("--warmup", type=int, default=350)
     ap.add_argument("--envs", type=int, default=N_ENVS, help="envs per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run and report what the headline does not need: headline_split, episodes_timed, "
+                         "roofline (isolated launches, STREAM peak, beyond-cache point), the all-gather check and "
+                         "the CPU baseline (the --no-*, --cpu-budget and --kernel-samples options shape these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the STREAM peak and beyond-cache point")
     ap.add_argument("--cpu-budget", type=float, default=2.5, help="seconds of CPU-baseline work per process")
@@ -619,7 +665,6 @@ def run(args, plat):
         return sum(week_bytes((w0 + i) % WEEKS + 1) for i in range(k))
 
     barrier = plat.barrier if coll else None
-    ev = [plat.new_event() for _ in range(4)]
 
     warmup_run = max(args.warmup, WEEKS)
     loop.run(warmup_run)
@@ -632,7 +677,43 @@ def run(args, plat):
         # headline: exactly K steps, unstamped (profiles/r02s_stamped_headline_ab.log)
         split = {}
         elapsed, _ = region(loop, args.steps, world, barrier, plat.sync, split=split)
-        gather.result()
+        gathered = gather.result()
+        dumped = snapshot_outputs(loop.last, gathered) if args.dump_outputs else None
+    finally:
+        gc.enable()
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, rank, world)
+    line = {
+        "metric": "env-steps/sec at 65536 envs/GPU, beergame-v0; 1/2/4/8 MI355X",
+        "value": None,
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "warmup_steps_run": warmup_run,
+        "ms_per_step": None,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic: Poisson(8) demand drawn on device (Philox4x32-10), uniform int [0,8] actions",
+        "config": {"workload": "beergame-v0 step() x 65536 envs/GPU (BASELINE configs[1]; configs[4] at N=8)",
+                   "n_envs_per_gpu": N, "levels": LEVELS, "weeks": WEEKS, "auto_reset": True,
+                   "ledgers": True, "orders_history": True, "episode_return_allgather": coll,
+                   "parallelism": f"env-shard x{world}"},
+    }
+    if not args.full:
+        env.check_errors()
+        gather.close()
+        (elapsed,) = max_over_ranks([elapsed], world, device, coll)
+        if rank != 0:
+            return None
+        line["value"], line["ms_per_step"] = N * world * args.steps / elapsed, elapsed * 1e3 / args.steps
+        line["episode_returns_gathered"] = gather.gathers
+        return line
+    ev = [plat.new_event() for _ in range(4)]
+    gc.disable()
+    try:
         # the fixed cost of a region: the same brackets around zero steps
         empty, _ = region(loop, 0, world, barrier, plat.sync)
         # 100 whole episodes, from an episode boundary
@@ -677,24 +758,8 @@ def run(args, plat):
         roof["measured_peak_source"] = ("scg_stream_copy of 1 GiB (read + write; one non-temporal 16-B "
                                         "vector per lane), 20 launches, same run")
         roof["beyond_cache"] = extras["beyond_cache"]
-    line = {
-        "metric": "env-steps/sec at 65536 envs/GPU, beergame-v0; 1/2/4/8 MI355X",
-        "value": N * world * args.steps / elapsed,
-        "unit": "env-steps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "warmup_steps_run": warmup_run,
-        "ms_per_step": elapsed * 1e3 / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int32",
-        "data": "synthetic: Poisson(8) demand drawn on device (Philox4x32-10), uniform int [0,8] actions",
-        "config": {"workload": "beergame-v0 step() x 65536 envs/GPU (BASELINE configs[1]; configs[4] at N=8)",
-                   "n_envs_per_gpu": N, "levels": LEVELS, "weeks": WEEKS, "auto_reset": True,
-                   "ledgers": True, "orders_history": True, "episode_return_allgather": coll,
-                   "parallelism": f"env-shard x{world}"},
+    line["value"], line["ms_per_step"] = N * world * args.steps / elapsed, elapsed * 1e3 / args.steps
+    line.update({
         "episodes_timed": {"episodes": EPISODES_TIMED, "steps": k_ep, "value": N * world * k_ep / ep_elapsed,
                            "ms_per_step": ep_elapsed * 1e3 / k_ep, "avg_kernel_us": ep_gpu_ms * 1e3 / k_ep,
                            "frac": ep_bytes / (ep_gpu_ms / 1e3) / 1e9 / HBM_PEAK_GBS},
@@ -712,7 +777,7 @@ def run(args, plat):
         "allgather_ok": gcheck["allgather_ok"],
         "gather_path": gcheck["gather_path"],
         "allgather_envs_checked": gcheck["envs_checked"],
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = plat.cpu_baseline(args.cpu_budget)
     return line
@@ -727,7 +792,7 @@ def main(argv=None):
     if plat.collectives:
         import torch.distributed as dist
         dist.destroy_process_group()
-    if line is not None and not line["allgather_ok"]:
+    if line is not None and not line.get("allgather_ok", True):
         sys.exit("bench: the episode-return all-gather does not hold every rank's returns in rank order")
 
 

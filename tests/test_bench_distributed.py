@@ -2,10 +2,12 @@
 barrier-bracketed timed region with the all_reduce-MAX aggregation, and the end-of-episode
 return all-gather across real auto-reset episode ends — with a CPU stand-in for the GPU
 batch env (oracle.beergame.BeerGameOracle per env, the device's Philox demand per global
-id). Rank 0's gathered returns must equal a 1-rank run over the concatenated shards. The
-last test runs bench.run() itself — the whole flow the driver's 8-GPU launch takes: warm-up,
-dry region, headline region, 100 stamped episodes, isolated launches, max over ranks and
-rank 0's JSON line — on 2, 4 and 8 gloo ranks with that stand-in as the platform."""
+id). Rank 0's gathered returns must equal a 1-rank run over the concatenated shards.
+test_bench_run_emits_the_rank0_line runs bench.run() itself with --full — the whole flow the
+driver's 8-GPU launch took: warm-up, dry region, headline region, 100 stamped episodes,
+isolated launches, max over ranks and rank 0's JSON line — on 2, 4 and 8 gloo ranks with that
+stand-in as the platform; the plain run (the headline only, --dump-outputs) runs on one rank
+in the test's own process."""
 import os
 import socket
 
@@ -202,7 +204,7 @@ def _run_worker(rank, world, port, q, collectives=None):
 
         gd.EpisodeReturnGather = RecordingGather
         plat = CpuPlatform(world, rank, collectives)
-        args = bench.parse_args(["--gpus", str(world), "--envs", "2", "--steps", "20", "--warmup", "5",
+        args = bench.parse_args(["--gpus", str(world), "--envs", "2", "--steps", "20", "--warmup", "5", "--full",
                                  "--kernel-samples", "35", "--no-extras", "--no-cpu-baseline"])
         line = bench.run(args, plat)
         gathered = seen["gather"].result().tolist()   # the last episode end's all-gather
@@ -263,6 +265,73 @@ def test_bench_run_emits_the_rank0_line(world):
     # the line's own content check of the last gather (EpisodeReturnGather.verify)
     assert line["allgather_ok"] is True and line["gather_path"] == "torch"
     assert line["allgather_envs_checked"] == world * n
+
+
+class ReturningBatch(StampedBatch):
+    """The stand-in with step() outputs like BeerGameVecEnv's: obs [n, 4], reward [n], done [n]."""
+
+    def step(self, actions, stamps=None):
+        week = self.week
+        _, _, _, info = super().step(actions, stamps)
+        obs = torch.as_tensor(np.asarray(actions), dtype=torch.int32) + week
+        rew = torch.full((self.n,), -week, dtype=torch.int32)
+        return obs, rew, torch.full((self.n,), bool(info)), info
+
+
+def test_plain_bench_run_times_only_the_headline_and_dumps_its_last_step(tmp_path):
+    """bench.run() without --full: warm-up, dry region and the K timed steps, nothing after;
+    the line keeps the headline keys and drops what --full reports. --dump-outputs writes
+    what the last timed step returned, float64, the same from run to run."""
+    import bench
+
+    class Plat(CpuPlatform):
+        def make_env(self, n_envs, env_offset):
+            self.env = ReturningBatch(n_envs, env_offset)
+            return self.env
+
+    def go(steps, out):
+        plat = Plat(1, 0, False)
+        line = bench.run(bench.parse_args(["--gpus", "1", "--envs", "3", "--steps", str(steps), "--warmup", "5",
+                                           "--dump-outputs", str(out)]), plat)
+        return plat, line
+
+    plat, line = go(35, tmp_path / "a")
+    assert plat.env.steps == 35 + 35 + 35                      # whole-episode warm-up, dry region, K steps
+    assert line["steps"] == 35 and line["warmup"] == 5 and line["warmup_steps_run"] == 70
+    assert line["metric"] == "env-steps/sec at 65536 envs/GPU, beergame-v0; 1/2/4/8 MI355X"
+    assert line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "int32"
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - 3 * 35 / (line["ms_per_step"] * 35 / 1e3)) < 1e-6 * line["value"]
+    for key in ("headline_split", "episodes_timed", "roofline", "cpu_baseline", "allgather_ok"):
+        assert key not in line
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["done", "episode_return_gathered", "info_episode_return", "obs", "reward"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    # the last timed step is week 35 of an episode: its action row plus 34, reward -34, done
+    want_obs = np.stack([np.asarray(a) for a in _week_actions(3, 0)[34]]) + 34
+    assert np.array_equal(got["obs"], want_obs) and np.array_equal(got["reward"], [-34.0] * 3)
+    assert np.array_equal(got["done"], [1.0] * 3)
+    assert np.array_equal(got["info_episode_return"], got["episode_return_gathered"])
+    go(35, tmp_path / "b")
+    for name, a in got.items():
+        assert np.array_equal(np.load(tmp_path / "b" / (name + ".npy")), a)
+    # --steps sets the number of timed steps; a last step inside an episode has no info arrays
+    plat, line = go(20, tmp_path / "c")
+    assert plat.env.steps == 35 + 20 + 20 and line["steps"] == 20
+    assert sorted(os.listdir(tmp_path / "c")) == ["done.npy", "episode_return_gathered.npy", "obs.npy", "reward.npy"]
+    assert np.array_equal(np.load(tmp_path / "c" / "done.npy"), [0.0] * 3)
+
+
+def test_dump_outputs_samples_rows_past_the_size_limit(tmp_path, monkeypatch):
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    arrays = {"obs": np.arange(4000, dtype=np.float64).reshape(1000, 4), "reward": np.arange(1000, dtype=np.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, rank=1, world=2)
+    obs, rew = np.load(tmp_path / "a" / "obs.npy"), np.load(tmp_path / "a" / "reward.npy")
+    assert obs.nbytes + rew.nbytes <= 4000 and len(obs) == len(rew) > 50
+    assert np.array_equal(obs[:, 0] / 4, rew) and np.all(np.diff(rew) > 0)   # the same rows of each, in order
+    assert np.array_equal(np.load(tmp_path / "b" / "obs_rank1.npy"), obs)
 
 
 def _verify_worker(rank, world, port, q, corrupt):

@@ -31,10 +31,10 @@ run() {  # run NAME SECONDS CMD...
 srchash() { python3 -c "import sys; sys.path.insert(0, '$ROOT'); import bench; print(bench.kernel_sources_hash('$1'))"; }
 want tests && run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
 want smoke && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-want bench && run bench 400 python bench.py
-want bench && run bench_driver 300 python bench.py --steps 20 --warmup 5
+want bench && run bench 400 python bench.py --full
+want bench && run bench_driver 300 python bench.py --steps 20 --warmup 5 --full
 want pg && run bench_pg 300 env SCG_BENCH_PG=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
+    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline
 want sc && run bench_sc 900 python tools/bench_sc.py --scenario all --kernel auto
 want led && run bench_sc_ledgers 600 python tools/bench_sc.py --scenario both --kernel auto --build-info --no-cpu-baseline
 want sweep && run sweep_bg 600 python tools/sweep_bg.py --max-log2 24
