@@ -53,6 +53,28 @@ __global__ __launch_bounds__(kBlock) void uniform_ints_kernel(uint32_t k0, uint3
   }
 }
 
+// Fills the slab kernel's constants block: the scalars travel by value, the thresholds are
+// copied on the device (0xffffffff past the table's end).
+__global__ __launch_bounds__(64) void bg_slab_consts_kernel(BgSlabConst* __restrict__ dst, const BgSlabConst v) {
+  const int q = threadIdx.x;
+  if (q < kFastThr) dst->thr[q] = (v.pthr && q < v.pthr_len) ? v.pthr[q] : 0xffffffffu;
+  if (q < SCG_BG_MAX_LEVELS) dst->init_inv[q] = v.init_inv[q];
+  if (q != 63) return;
+  dst->env_base = v.env_base;
+  dst->pthr_len = v.pthr_len;
+  dst->h = v.h;
+  dst->b = v.b;
+  dst->guard = v.guard;
+  dst->demand_lo = v.demand_lo;
+  dst->demand_hi = v.demand_hi;
+  dst->ship_value = v.ship_value;
+  dst->orders_value = v.orders_value;
+  dst->init_slots = v.init_slots;
+  dst->err_host = v.err_host;
+  dst->demand_table = v.demand_table;
+  dst->pthr = v.pthr;
+}
+
 // ---- host helpers: run-time dispatch on the level count ----------------------------------
 int launch_reset(int L, dim3 grid, hipStream_t s, const BgArgs& a) {
   switch (L) {
@@ -92,11 +114,10 @@ int launch_server(int L, int demand_mode, hipStream_t s, scg_bg_server_box* box,
   }
 }
 
-int launch_slab(int demand_mode, int L, dim3 grid, hipStream_t s, int32_t* slab, const int32_t* act, int32_t* out,
-                uint32_t n32, uint32_t wpack, uint32_t week, uint32_t episode, uint32_t k0, uint32_t k1,
-                const BgSlabArgs& a, hipEvent_t ev0, hipEvent_t ev1) {
+int launch_slab(int demand_mode, int L, dim3 grid, hipStream_t s, const SlabLaunch& a, hipEvent_t ev0,
+                hipEvent_t ev1) {
   switch (L) {
-#define X(l) case l: return bg_launch_slab<l>(demand_mode, grid, s, slab, act, out, n32, wpack, week, episode, k0, k1, a, ev0, ev1);
+#define X(l) case l: return bg_launch_slab<l>(demand_mode, grid, s, a, ev0, ev1);
     SCG_LEVEL_CASES(X)
 #undef X
     default: return fail(SCG_ERR_INVALID, "levels=%d outside 1..%d", L, SCG_BG_MAX_LEVELS);
@@ -129,11 +150,11 @@ int slab_layout(int L, int64_t N, int32_t R, int32_t T, bool history, int64_t* o
   return SCG_OK;
 }
 
-// The slab kernel runs when st->slab is set, its views are where the layout puts them and
-// the rewards follow the observation rows in one allocation.
+// The slab kernel runs when st->slab and st->step_consts are set, the slab's views are where
+// the layout puts them and the rewards follow the observation rows in one allocation.
 bool slab_ready(const scg_bg_config* cfg, const scg_bg_state* st, const int32_t* obs, const int32_t* reward,
                 const int32_t* terminal_obs) {
-  if (!st->slab || cfg->variant != 1) return false;
+  if (!st->slab || !st->step_consts || cfg->variant != 1) return false;
   int64_t off[SCG_SLAB_FIELDS];
   const bool hist = st->orders_history != nullptr;
   if (slab_layout(cfg->levels, st->n_envs, cfg->ring_slots, cfg->max_weeks, hist, off) != SCG_OK) return false;
@@ -220,6 +241,55 @@ BgArgs make_args(const scg_bg_config* cfg, const scg_bg_state* st) {
 }
 
 inline dim3 grid_for(int64_t n) { return dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)); }
+
+// What the slab kernel's constants block holds for (cfg, st): every scalar, and the
+// thresholds by pointer and length (the fill kernel copies them on the device).
+BgSlabConst slab_consts(const scg_bg_config* cfg, const scg_bg_state* st) {
+  BgSlabConst v;
+  std::memset(&v, 0, sizeof(v));
+  v.env_base = static_cast<uint32_t>(st->env_offset);
+  v.pthr_len = cfg->demand_mode == SCG_DEMAND_POISSON ? cfg->poisson_len : 0;
+  v.h = cfg->inv_cost;
+  v.b = cfg->backlog_cost;
+  v.guard = week_guard(cfg->levels, cfg->inv_cost, cfg->backlog_cost);
+  v.demand_lo = cfg->demand_lo;
+  v.demand_hi = cfg->demand_hi;
+  v.ship_value = cfg->initial_shipment_value;
+  v.orders_value = cfg->initial_orders_value;
+  v.init_slots = init_slots(cfg);
+  v.err_host = st->error_host;
+  v.demand_table = cfg->demand_table;
+  v.pthr = cfg->demand_mode == SCG_DEMAND_POISSON ? cfg->poisson_thresholds : nullptr;
+  for (int l = 0; l < cfg->levels; ++l) v.init_inv[l] = cfg->initial_inventory[l];
+  return v;
+}
+
+// Fingerprint of a block's contents and address (never 0: 0 is "nothing uploaded").
+uint64_t slab_consts_tag(const BgSlabConst& v, const void* block) {
+  static_assert(offsetof(BgSlabConst, thr) % 8 == 0, "hashed as 64-bit words");
+  uint64_t w[offsetof(BgSlabConst, thr) / 8];
+  std::memcpy(w, &v, sizeof(w));
+  uint64_t h = 0x9E3779B97F4A7C15ull ^ reinterpret_cast<uintptr_t>(block);
+  for (uint64_t x : w) {
+    h = (h ^ x) * 0xFF51AFD7ED558CCDull;
+    h ^= h >> 29;
+  }
+  return h | 1u;
+}
+
+// Uploads the block, in stream order ahead of the step, when it does not hold what this
+// step needs (first step, or cfg / st edited since).
+int sync_slab_consts(const scg_bg_config* cfg, scg_bg_state* st, hipStream_t s) {
+  const BgSlabConst v = slab_consts(cfg, st);
+  const uint64_t tag = slab_consts_tag(v, st->step_consts);
+  if (tag == st->step_consts_tag) return SCG_OK;
+  if (reinterpret_cast<uintptr_t>(st->step_consts) % alignof(BgSlabConst) != 0)
+    return fail(SCG_ERR_INVALID, "step_consts must be %d-byte aligned", static_cast<int>(alignof(BgSlabConst)));
+  hipLaunchKernelGGL(bg_slab_consts_kernel, dim3(1), dim3(64), 0, s, static_cast<BgSlabConst*>(st->step_consts), v);
+  if (int rc = check_launch("bg_slab_consts_kernel")) return rc;
+  st->step_consts_tag = tag;
+  return SCG_OK;
+}
 
 }  // namespace scg
 
@@ -367,23 +437,7 @@ int scg_bg_step_timed(const scg_bg_config* cfg, scg_bg_state* st, const int32_t*
   const int32_t w = st->week + 1;
   const WeekInfo wk = week_info(cfg, w, flags);
   if (slab_ready(cfg, st, obs, reward, terminal_obs)) {
-    BgSlabArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.pthr = cfg->poisson_thresholds;
-    sa.demand_table = cfg->demand_table;
-    sa.pthr_len = cfg->poisson_len;
-    sa.h = cfg->inv_cost;
-    sa.b = cfg->backlog_cost;
-    sa.demand_fixed = wk.demand_fixed;
-    sa.demand_lo = cfg->demand_lo;
-    sa.demand_hi = cfg->demand_hi;
-    sa.ship_value = cfg->initial_shipment_value;
-    sa.orders_value = cfg->initial_orders_value;
-    sa.init_slots = init_slots(cfg);
-    sa.env_offset = st->env_offset;
-    sa.guard = week_guard(cfg->levels, cfg->inv_cost, cfg->backlog_cost);
-    sa.err_host = st->error_host;
-    for (int l = 0; l < cfg->levels; ++l) sa.init_inv[l] = cfg->initial_inventory[l];
+    if (int rc = sync_slab_consts(cfg, st, static_cast<hipStream_t>(stream))) return rc;
     uint32_t wpack = pack_week_slab(wk);  // R <= 127 (slab_layout)
     wpack |= (wk.flags & 1) ? SW_TERMINAL : 0u;
     wpack |= (wk.flags & 2) ? SW_AUTORESET : 0u;
@@ -391,11 +445,11 @@ int scg_bg_step_timed(const scg_bg_config* cfg, scg_bg_state* st, const int32_t*
     wpack |= st->episode_return ? SW_RETURNS : 0u;
     wpack |= st->orders_history ? SW_HISTORY : 0u;
     wpack |= static_cast<uint32_t>(cfg->ring_slots) << 24;
-    if (int rc = launch_slab(cfg->demand_mode, cfg->levels, grid_for(st->n_envs), static_cast<hipStream_t>(stream),
-                             st->slab, action, obs, static_cast<uint32_t>(st->n_envs), wpack, static_cast<uint32_t>(w),
-                             st->episode, static_cast<uint32_t>(st->seed & 0xffffffffu),
-                             static_cast<uint32_t>(st->seed >> 32), sa, static_cast<hipEvent_t>(start_event),
-                             static_cast<hipEvent_t>(stop_event)))
+    const SlabLaunch sl{st->slab, action, obs, static_cast<const BgSlabConst*>(st->step_consts), st->seed,
+                        static_cast<uint32_t>(st->n_envs), wpack, static_cast<uint32_t>(w), st->episode,
+                        wk.demand_fixed};
+    if (int rc = launch_slab(cfg->demand_mode, cfg->levels, grid_for(st->n_envs), static_cast<hipStream_t>(stream), sl,
+                             static_cast<hipEvent_t>(start_event), static_cast<hipEvent_t>(stop_event)))
       return rc;
     if (wk.flags & 2) {
       st->week = 0;

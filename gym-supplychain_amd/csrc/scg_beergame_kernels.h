@@ -152,6 +152,8 @@ __device__ __forceinline__ void store_row(int32_t* __restrict__ p, const int32_t
 #define SCG_BG_STORE 1
 #endif
 typedef int v4i32 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 
 template <int L>
 __device__ __forceinline__ void store_row_p(int32_t* __restrict__ p, const int32_t (&v)[L]) {
@@ -195,6 +197,27 @@ __device__ __forceinline__ void fill_row(int32_t* __restrict__ p, int32_t x) {
 __device__ __forceinline__ int32_t poisson_count_scalar(ConstTab<uint32_t> thr, int32_t len, uint32_t u) {
   int32_t x = 0;
   int k = 0;
+  for (; k + 8 <= len; k += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x += (thr[k + j] <= u) ? 1 : 0;
+  }
+  for (; k < len; ++k) x += (thr[k] <= u) ? 1 : 0;
+  return x;
+}
+
+// The same count with the first kFastThr thresholds already in registers, padded with
+// 0xffffffff past the table's end: x = #{q < kFastThr : fast[q] <= u}, then min(x, len). A pad
+// counts only when u == 0xffffffff, where every real entry counts too, so the true count is
+// len and the min restores it. Tables longer than kFastThr go on through `thr` from entry
+// kFastThr (there fast[] holds no pad and the min changes nothing).
+constexpr int kFastThr = 40;
+__host__ __device__ __forceinline__ int32_t poisson_count_padded(const uint32_t (&fast)[kFastThr],
+                                                                 ConstTab<uint32_t> thr, int32_t len, uint32_t u) {
+  int32_t x = 0;
+#pragma unroll
+  for (int q = 0; q < kFastThr; ++q) x += (fast[q] <= u) ? 1 : 0;
+  x = x < len ? x : len;
+  int k = kFastThr;
   for (; k + 8 <= len; k += 8) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) x += (thr[k + j] <= u) ? 1 : 0;
@@ -663,24 +686,28 @@ __global__ __launch_bounds__(kServerBlock) void bg_server_kernel(scg_bg_server_b
 // The same week with every state row at a fixed offset from one base pointer (the slab,
 // scg_bg_slab_layout): inventory, backlog, orders, both ledgers, the terminal observation,
 // the ring slots, both returns and the history. The leading arguments — slab, actions,
-// outputs (obs rows then rewards), env count, week plan, week, episode and the Philox key
-// (12 dwords) — are preloaded into SGPRs at wave launch, so every row load and store is
-// addressed without reading the kernarg segment; only the costs, the Poisson table pointer
-// and the reset values arrive through scalar loads, which overlap the rows in flight.
-struct BgSlabArgs {
-  const uint32_t* pthr;
-  const int32_t* demand_table;
+// outputs (obs rows then rewards), the constants block, the Philox key, env count, week
+// plan, week and episode (14 dwords; with the kernarg pointer the 16 user SGPRs there are) —
+// are preloaded into SGPRs at wave launch, so every row load and store is addressed without
+// reading the kernarg segment. Whatever else a launch needs is fixed once the env is built
+// and lives in a device block (scg_bg_state.step_consts, filled by bg_slab_consts_kernel):
+// right behind the row loads the wave reads it in one round of scalar loads, thresholds
+// included, and waits once; nothing on the regular path reads a scalar after that.
+struct alignas(64) BgSlabConst {
+  uint32_t env_base;   // (uint32_t)env_offset: Philox counts env_base + n
   int32_t pthr_len;
-  int32_t h, b;
-  int32_t demand_fixed;
+  int32_t h, b, guard;
   int32_t demand_lo, demand_hi;
   int32_t ship_value, orders_value, init_slots;
-  int64_t env_offset;
-  int32_t guard;
   int32_t* err_host;
+  const int32_t* demand_table;
+  const uint32_t* pthr;
   int32_t init_inv[SCG_BG_MAX_LEVELS];
+  uint32_t thr[kFastThr];  // pthr[0 .. kFastThr), 0xffffffff past pthr_len
 };
-
+static_assert(sizeof(BgSlabConst) <= SCG_BG_STEP_CONSTS_BYTES && offsetof(BgSlabConst, err_host) == 40 &&
+                  offsetof(BgSlabConst, init_inv) == 64 && offsetof(BgSlabConst, thr) == 128,
+              "BgSlabConst layout");
 
 // wpack bits of the slab kernel
 constexpr uint32_t SW_TERMINAL = 1u << 18, SW_AUTORESET = 1u << 19, SW_LEDGERS = 1u << 20, SW_RETURNS = 1u << 21,
@@ -689,11 +716,14 @@ constexpr int kSlabHeader = 4;  // int32 words before the first row (the error w
 
 template <int L, int DM>
 __global__ __launch_bounds__(kBlock) void bg_step_slab_kernel(int32_t* __restrict__ slab, const int32_t* __restrict__ act_p,
-                                                              int32_t* __restrict__ out, uint32_t n32, uint32_t wpack,
-                                                              uint32_t week, uint32_t episode, uint32_t key0,
-                                                              uint32_t key1, const BgSlabArgs a) {
+                                                              int32_t* __restrict__ out,
+                                                              const BgSlabConst* __restrict__ consts, uint64_t key,
+                                                              uint32_t n32, uint32_t wpack, uint32_t week,
+                                                              uint32_t episode, int32_t demand_fixed) {
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (n >= static_cast<int64_t>(n32)) return;
+  const ConstTab<BgSlabConst> c = const_tab(consts);
+  const uint32_t key0 = static_cast<uint32_t>(key), key1 = static_cast<uint32_t>(key >> 32);
   const int32_t read_slot = static_cast<int32_t>(wpack & 0xffu) - 1;
   const int32_t write_slot = static_cast<int32_t>((wpack >> 8) & 0xffu);
   const int32_t mode = static_cast<int32_t>((wpack >> 16) & 3u);
@@ -726,25 +756,53 @@ __global__ __launch_bounds__(kBlock) void bg_step_slab_kernel(int32_t* __restric
     load_row<L>(bacc_p + row, bacc);
   }
   const int64_t ret0 = returns ? ret_p[n] : 0;
-  export_error(n, terminal, slab, a.err_host);
+  // Every regular-path constant in one scalar round behind the row loads (the error word is
+  // exported only after the demand is drawn: a branch in between would split the round).
+  // Left alone the compiler moves some of these loads behind Philox, or into the block that
+  // uses them, and waits again there; the empty asm statement of each mode needs every value
+  // of the round in SGPRs at that point, so the round is issued, and waited for once, there.
+  const int32_t h = c->h, b = c->b, guard = c->guard;
+  int32_t* const err_host = c->err_host;
   int32_t demand;
   if constexpr (DM == SCG_DEMAND_FIXED) {
-    demand = a.demand_fixed;
+    demand = demand_fixed;
+    asm volatile("" : "+s"(demand) : "s"(h), "s"(b), "s"(guard), "s"(err_host));
   } else if constexpr (DM == SCG_DEMAND_TABLE) {
-    demand = a.demand_table[static_cast<int64_t>(week - 1) * n32 + n];
+    const int32_t* table = c->demand_table;
+    asm volatile("" : "+s"(table) : "s"(h), "s"(b), "s"(guard), "s"(err_host));
+    demand = table[static_cast<int64_t>(week - 1) * n32 + n];
   } else if constexpr (DM == SCG_DEMAND_UNIFORM) {
-    const uint32_t w = scg::philox_word(key0, key1, static_cast<uint32_t>(a.env_offset + n), episode, week - 1,
+    const int32_t lo = c->demand_lo, hi = c->demand_hi;
+    uint32_t env_base = c->env_base;
+    asm volatile("" : "+s"(env_base) : "s"(lo), "s"(hi), "s"(h), "s"(b), "s"(guard), "s"(err_host));
+    const uint32_t w = scg::philox_word(key0, key1, env_base + static_cast<uint32_t>(n), episode, week - 1,
                                         SCG_STREAM_BG2_DEMAND);
-    demand = a.demand_lo + static_cast<int32_t>((static_cast<uint64_t>(w) * static_cast<uint32_t>(a.demand_hi - a.demand_lo)) >> 32);
+    demand = lo + static_cast<int32_t>((static_cast<uint64_t>(w) * static_cast<uint32_t>(hi - lo)) >> 32);
   } else {
-    const uint32_t u = scg::philox_word(key0, key1, static_cast<uint32_t>(a.env_offset + n), episode, week - 1,
+    static_assert(kFastThr == 40, "the thresholds are read as 16 + 16 + 8 dwords");
+    const u32x16 t0 = *reinterpret_cast<ConstTab<u32x16>>(c->thr);
+    const u32x16 t1 = *reinterpret_cast<ConstTab<u32x16>>(c->thr + 16);
+    const u32x8 t2 = *reinterpret_cast<ConstTab<u32x8>>(c->thr + 32);
+    const int32_t len = c->pthr_len;
+    const ConstTab<uint32_t> pthr = const_tab(c->pthr);
+    // (the threshold loads would move behind Philox: 40 SGPRs less to keep across it)
+    uint32_t env_base = c->env_base;
+    asm volatile("" : "+s"(env_base) : "s"(t0), "s"(t1), "s"(t2), "s"(len), "s"(pthr), "s"(h), "s"(b), "s"(guard),
+                 "s"(err_host));
+    uint32_t fast[kFastThr];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) fast[q] = t0[q], fast[16 + q] = t1[q];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) fast[32 + q] = t2[q];
+    const uint32_t u = scg::philox_word(key0, key1, env_base + static_cast<uint32_t>(n), episode, week - 1,
                                         SCG_STREAM_DEMAND);
-    demand = poisson_count_scalar(const_tab(a.pthr), a.pthr_len, u);
+    demand = poisson_count_padded(fast, pthr, len, u);
   }
+  export_error(n, terminal, slab, err_host);
 
   int32_t ship[L], obs[L];
   bool ovf = false;
-  const int32_t reward = week_update<L>(a.h, a.b, a.guard, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship,
+  const int32_t reward = week_update<L>(h, b, guard, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship,
                                         obs, cur, iacc, bacc, ovf);
   if (mode == MODE_STORE) {
     store_row_p<L>(ring_p + write_slot * NL + row, ship);
@@ -761,17 +819,18 @@ __global__ __launch_bounds__(kBlock) void bg_step_slab_kernel(int32_t* __restric
   if (autoreset) {  // reset() in the same launch (:140-156)
     int32_t v[L];
 #pragma unroll
-    for (int l = 0; l < L; ++l) v[l] = a.init_inv[l];
+    for (int l = 0; l < L; ++l) v[l] = c->init_inv[l];
+    const int32_t orders_value = c->orders_value, ship_value = c->ship_value, init_slots = c->init_slots;
     store_row_p<L>(inv_p + row, v);
     store_row_p<L>(out + row, v);                                              // reset obs: inventory - 0
     fill_row_p<L>(bk_p + row, 0);
-    fill_row_p<L>(op_p + row, a.orders_value);
-    for (int t = 1; t <= a.init_slots; ++t) fill_row_p<L>(ring_p + (t % R) * NL + row, a.ship_value);
+    fill_row_p<L>(op_p + row, orders_value);
+    for (int t = 1; t <= init_slots; ++t) fill_row_p<L>(ring_p + (t % R) * NL + row, ship_value);
     if (ledgers) {
       fill_row_p<L>(iacc_p + row, 0);
       fill_row_p<L>(bacc_p + row, 0);
     }
-    if (history) fill_row_p<L>(hist_p + row, a.orders_value);
+    if (history) fill_row_p<L>(hist_p + row, orders_value);
     if (returns) ret_p[n] = 0;
     note_overflow(slab, ovf);
     return;
@@ -1055,14 +1114,23 @@ __global__ __launch_bounds__(kBlock) void bg_rollout_lds_kernel(const BgArgs a, 
 // hipModuleLaunchKernel with the kernel's function handle resolved once per instantiation,
 // skipping the host-stub lookup of hipLaunchKernel on every step: ≈0.5 µs less host time
 // per step (tools/short_region.py, profiles/r02h_short_region.log).
+// The slab kernel's arguments, in its order.
+struct SlabLaunch {
+  int32_t* slab;
+  const int32_t* act;
+  int32_t* out;
+  const BgSlabConst* consts;
+  uint64_t key;  // key0 | key1 << 32
+  uint32_t n32, wpack, week, episode;
+  int32_t demand_fixed;
+};
+
 template <int L, int DM>
-int launch_slab_module(dim3 grid, hipStream_t s, int32_t* slab, const int32_t* act, int32_t* out, uint32_t n32,
-                       uint32_t wpack, uint32_t week, uint32_t episode, uint32_t k0, uint32_t k1, const BgSlabArgs& a) {
+int launch_slab_module(dim3 grid, hipStream_t s, SlabLaunch a) {
   static hipFunction_t fn = nullptr;
   if (!fn && hipGetFuncBySymbol(&fn, reinterpret_cast<const void*>(&bg_step_slab_kernel<L, DM>)) != hipSuccess)
     return fail(SCG_ERR_HIP, "hipGetFuncBySymbol(bg_step_slab_kernel) failed");
-  BgSlabArgs args = a;
-  void* params[] = {&slab, &act, &out, &n32, &wpack, &week, &episode, &k0, &k1, &args};
+  void* params[] = {&a.slab, &a.act, &a.out, &a.consts, &a.key, &a.n32, &a.wpack, &a.week, &a.episode, &a.demand_fixed};
   if (hipModuleLaunchKernel(fn, grid.x, 1, 1, kBlock, 1, 1, 0, s, params, nullptr) != hipSuccess)
     return fail(SCG_ERR_HIP, "hipModuleLaunchKernel(bg_step_slab_kernel) failed");
   return SCG_OK;
@@ -1123,35 +1191,25 @@ int bg_launch_server(hipStream_t s, int demand_mode, scg_bg_server_box* box, uin
 }
 
 template <int L, int DM>
-int bg_launch_slab_dm(dim3 grid, hipStream_t s, int32_t* slab, const int32_t* act, int32_t* out, uint32_t n32,
-                      uint32_t wpack, uint32_t week, uint32_t episode, uint32_t k0, uint32_t k1, const BgSlabArgs& a,
-                      hipEvent_t ev0, hipEvent_t ev1) {
+int bg_launch_slab_dm(dim3 grid, hipStream_t s, const SlabLaunch& a, hipEvent_t ev0, hipEvent_t ev1) {
   if (ev0 || ev1) {
-    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_slab_kernel<L, DM>), grid, dim3(kBlock), 0, s, ev0, ev1, 0, slab, act,
-                          out, n32, wpack, week, episode, k0, k1, a);
+    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_slab_kernel<L, DM>), grid, dim3(kBlock), 0, s, ev0, ev1, 0, a.slab,
+                          a.act, a.out, a.consts, a.key, a.n32, a.wpack, a.week, a.episode, a.demand_fixed);
     return check_launch("bg_step_slab_kernel");
   }
-  if (SCG_MODULE_LAUNCH) return launch_slab_module<L, DM>(grid, s, slab, act, out, n32, wpack, week, episode, k0, k1, a);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_slab_kernel<L, DM>), grid, dim3(kBlock), 0, s, slab, act, out, n32, wpack,
-                     week, episode, k0, k1, a);
+  if (SCG_MODULE_LAUNCH) return launch_slab_module<L, DM>(grid, s, a);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_slab_kernel<L, DM>), grid, dim3(kBlock), 0, s, a.slab, a.act, a.out,
+                     a.consts, a.key, a.n32, a.wpack, a.week, a.episode, a.demand_fixed);
   return check_launch("bg_step_slab_kernel");
 }
 
 template <int L>
-int bg_launch_slab(int demand_mode, dim3 grid, hipStream_t s, int32_t* slab, const int32_t* act, int32_t* out,
-                   uint32_t n32, uint32_t wpack, uint32_t week, uint32_t episode, uint32_t k0, uint32_t k1,
-                   const BgSlabArgs& a, hipEvent_t ev0, hipEvent_t ev1) {
+int bg_launch_slab(int demand_mode, dim3 grid, hipStream_t s, const SlabLaunch& a, hipEvent_t ev0, hipEvent_t ev1) {
   switch (demand_mode) {
-    case SCG_DEMAND_FIXED:
-      return bg_launch_slab_dm<L, SCG_DEMAND_FIXED>(grid, s, slab, act, out, n32, wpack, week, episode, k0, k1, a, ev0, ev1);
-    case SCG_DEMAND_TABLE:
-      return bg_launch_slab_dm<L, SCG_DEMAND_TABLE>(grid, s, slab, act, out, n32, wpack, week, episode, k0, k1, a, ev0, ev1);
-    case SCG_DEMAND_UNIFORM:
-      return bg_launch_slab_dm<L, SCG_DEMAND_UNIFORM>(grid, s, slab, act, out, n32, wpack, week, episode, k0, k1, a, ev0,
-                                                      ev1);
-    default:
-      return bg_launch_slab_dm<L, SCG_DEMAND_POISSON>(grid, s, slab, act, out, n32, wpack, week, episode, k0, k1, a, ev0,
-                                                      ev1);
+    case SCG_DEMAND_FIXED: return bg_launch_slab_dm<L, SCG_DEMAND_FIXED>(grid, s, a, ev0, ev1);
+    case SCG_DEMAND_TABLE: return bg_launch_slab_dm<L, SCG_DEMAND_TABLE>(grid, s, a, ev0, ev1);
+    case SCG_DEMAND_UNIFORM: return bg_launch_slab_dm<L, SCG_DEMAND_UNIFORM>(grid, s, a, ev0, ev1);
+    default: return bg_launch_slab_dm<L, SCG_DEMAND_POISSON>(grid, s, a, ev0, ev1);
   }
 }
 
@@ -1175,9 +1233,7 @@ int bg_launch_rollout(dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, cons
   EXT template int bg_launch_step2<l>(dim3, hipStream_t, const BgArgs&, const WeekInfo&);                           \
   EXT template int bg_launch_step<l>(dim3, hipStream_t, const BgArgs&, const WeekInfo&, hipEvent_t, hipEvent_t);    \
   EXT template int bg_launch_server<l>(hipStream_t, int, scg_bg_server_box*, uint32_t, uint32_t);                   \
-  EXT template int bg_launch_slab<l>(int, dim3, hipStream_t, int32_t*, const int32_t*, int32_t*, uint32_t, uint32_t, \
-                                     uint32_t, uint32_t, uint32_t, uint32_t, const BgSlabArgs&, hipEvent_t,         \
-                                     hipEvent_t);                                                                    \
+  EXT template int bg_launch_slab<l>(int, dim3, hipStream_t, const SlabLaunch&, hipEvent_t, hipEvent_t);            \
   EXT template int bg_launch_rollout<l>(dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&,             \
                                         const int32_t*, int32_t*, int32_t*);
 #define SCG_BG_EXTERN_LEVEL(l) SCG_BG_LAUNCHERS(extern, l)

@@ -16,7 +16,7 @@ import torch  # noqa: F401  (loads the HIP runtime libscgpu.so binds to)
 
 LIB_NAME = "libscgpu.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 SCG_OK = 0
 SCG_ERR_INVALID = 1
@@ -99,7 +99,12 @@ class BgState(ctypes.Structure):
         ("error_flags", ctypes.c_void_p),
         ("error_host", ctypes.c_void_p),
         ("slab", ctypes.c_void_p),
+        ("step_consts", ctypes.c_void_p),
+        ("step_consts_tag", ctypes.c_uint64),
     ]
+
+
+BG_STEP_CONSTS_BYTES = 512  # SCG_BG_STEP_CONSTS_BYTES: the slab step kernel's constants block
 
 
 BG_SERVER_SLOTS = 15

@@ -209,9 +209,12 @@ class BeerGameVecEnv:
         # them all from one base), or separate tensors when N * L is not a multiple of 4
         v2 = c.variant == 2
         off = (ctypes.c_int64 * nat.SLAB_FIELDS)()
-        self._slab = None
+        self._slab = self._step_consts = None
         if state_slab and nat.lib.scg_bg_slab_layout(ctypes.byref(c), n_envs, int(bool(track_history)), off) == 0:
             self._slab = torch.zeros(off[nat.SLAB_TOTAL], **i32)
+            # the slab kernel's launch constants (derived from the config, not state: the
+            # library fills the block in stream order and refills it when the config changes)
+            self._step_consts = torch.zeros(nat.BG_STEP_CONSTS_BYTES // 4, **i32)
 
             def rows(field, k=1):
                 return self._slab[off[field]: off[field] + k * n_envs * L].view(*((k,) if k > 1 else ()), n_envs, L)
@@ -267,6 +270,8 @@ class BeerGameVecEnv:
         s.error_flags = self._err.data_ptr()
         s.error_host = self._err_word.dev
         s.slab = self._slab.data_ptr() if self._slab is not None else None
+        s.step_consts = self._step_consts.data_ptr() if self._step_consts is not None else None
+        s.step_consts_tag = 0
         self._st = s
         self._cfg_ref = ctypes.byref(self._cfg)
         self._st_ref = ctypes.byref(self._st)

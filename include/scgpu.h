@@ -41,8 +41,10 @@ extern "C" {
  *   scg_bg_server_stop) and the testing hook scg_sc_nodes_max_blocks.
  * 7 (round 6): the step server serves up to SCG_BG_SERVER_SLOTS envs from one wave
  *   (scg_bg_server_slot, attach / detach / post / wait), mixing-hash check word; the
- *   SupplyChain step server (scg_sc_server_box, scg_sc_server, scg_sc_server_*). */
-#define SCG_ABI_VERSION 7
+ *   SupplyChain step server (scg_sc_server_box, scg_sc_server, scg_sc_server_*).
+ * 8: scg_bg_state ends with step_consts / step_consts_tag: the device block of the slab
+ *   step kernel's launch constants (SCG_BG_STEP_CONSTS_BYTES). */
+#define SCG_ABI_VERSION 8
 
 #if defined(__GNUC__)
 #define SCG_API __attribute__((visibility("default")))
@@ -152,10 +154,24 @@ typedef struct scg_bg_state {
    * without synchronising (read it after a later episode's terminal step has completed). */
   int32_t* error_host;
   /* Optional state slab (scg_bg_slab_layout): when non-NULL, every buffer above must be
-   * the slab view the layout names, and scg_bg_step launches the slab step kernel, which
-   * addresses every row from this one base. */
+   * the slab view the layout names, and scg_bg_step launches the slab step kernel (given
+   * step_consts below too), which addresses every row from this one base. */
   int32_t* slab;
+  /* Optional DEVICE block of SCG_BG_STEP_CONSTS_BYTES bytes, 64-byte aligned, that the slab
+   * step kernel reads its launch constants from (costs, guard, reset values, env_offset,
+   * error_host, the demand table pointers and the first Poisson thresholds: everything that
+   * is fixed once the env is built) in one round of scalar loads. The caller only allocates
+   * it; the library fills it in stream order, by a small kernel ahead of the step, whenever
+   * step_consts_tag differs from the fingerprint of cfg / st the step is called with (so
+   * editing cfg between steps is safe; the contents of poisson_thresholds are fingerprinted
+   * by pointer and length only). NULL: scg_bg_step runs the general step kernel, slab or not. */
+  void* step_consts;
+  /* Host: fingerprint of what step_consts holds (0: nothing). Zero it after writing the block
+   * or the threshold table by other means. */
+  uint64_t step_consts_tag;
 } scg_bg_state;
+
+#define SCG_BG_STEP_CONSTS_BYTES 512
 
 /* Slab fields, in order: word offsets filled by scg_bg_slab_layout. */
 enum scg_bg_slab_field {
@@ -209,7 +225,8 @@ SCG_API int scg_bg_prepare(scg_bg_config* cfg);
  * Word offsets of one state slab for n_envs envs of a prepared cfg (ring_slots known),
  * with the order history when with_history != 0. Host only; the caller allocates
  * offsets[SCG_SLAB_TOTAL] int32 words of DEVICE memory (16-byte aligned, zeroed), points
- * the scg_bg_state buffers at base + offsets[field] and sets st->slab = base.
+ * the scg_bg_state buffers at base + offsets[field] and sets st->slab = base (and, outside
+ * the slab, st->step_consts to SCG_BG_STEP_CONSTS_BYTES of its own).
  */
 SCG_API int scg_bg_slab_layout(const scg_bg_config* cfg, int64_t n_envs, int32_t with_history,
                                int64_t offsets[SCG_SLAB_FIELDS]);
@@ -226,8 +243,10 @@ SCG_API int scg_bg_reset(const scg_bg_config* cfg, scg_bg_state* st, int32_t* ob
  *   terminal_obs DEVICE int32 [N][L] or NULL: observation at the terminal week
  * Returns SCG_ERR_PAST_HORIZON when called after the terminal week without auto-reset.
  * Sets *done (host, may be NULL) to 1 when this step was the terminal week (:134).
- * With st->slab set, reward == obs + N*L (one output allocation) and terminal_obs NULL or the
- * slab's SCG_SLAB_TERMINAL_OBS view, the slab kernel runs (terminal obs into the slab).
+ * With st->slab and st->step_consts set, reward == obs + N*L (one output allocation) and
+ * terminal_obs NULL or the slab's SCG_SLAB_TERMINAL_OBS view, the slab kernel runs (terminal
+ * obs into the slab); a step whose st->step_consts_tag is stale first launches the small kernel
+ * that fills the block. Otherwise the general step kernel runs, with the same results.
  */
 SCG_API int scg_bg_step(const scg_bg_config* cfg, scg_bg_state* st, const int32_t* action,
                 int32_t* obs, int32_t* reward, int32_t* terminal_obs, uint32_t flags,
