@@ -86,12 +86,7 @@ struct BgArgs {
 
 // The reference computes in int64 (beergame_env.py:33,35,130-132); the kernels compute each
 // week in int64 too and store int32, noting whether every stored value fits.
-#ifndef SCG_BG_OVERFLOW_CHECK
-#define SCG_BG_OVERFLOW_CHECK 1  // 0 only for A/B timing builds (tools/exp_build.py -D)
-#endif
-__device__ __forceinline__ bool fits32(int64_t x) {
-  return !SCG_BG_OVERFLOW_CHECK || x == static_cast<int64_t>(static_cast<int32_t>(x));
-}
+__device__ __forceinline__ bool fits32(int64_t x) { return x == static_cast<int64_t>(static_cast<int32_t>(x)); }
 __device__ __forceinline__ int out32(int64_t x) { return fits32(x) ? 0 : 1; }
 
 // Sets bit 0 of the error word when this lane saw a value outside int32: a plain vector
@@ -143,30 +138,21 @@ __device__ __forceinline__ void store_row(int32_t* __restrict__ p, const int32_t
   }
 }
 
-// Row stores of the slab kernel, by policy (SCG_BG_STORE): 0 plain, 1 non-temporal (nt),
-// 2 write-through (sc1: the bytes leave L2 as they are stored and the line is dropped).
-// A/B on one box (profiles/r02j_bg_store_ab.log, 65,536 envs): back-to-back launches 4.73-4.79
-// (plain) / 4.61 (nt) / 5.05-5.07 µs (sc1) per step; launches run alone 5.36-5.41 / 5.16 /
-// 4.73 µs. The bench and a training loop run launches back to back, so nt is the default.
-#ifndef SCG_BG_STORE
-#define SCG_BG_STORE 1
-#endif
+// Row stores of the slab kernel: non-temporal (nt). A/B on one box against plain and
+// write-through (sc1) stores (profiles/r02j_bg_store_ab.log, 65,536 envs): back-to-back
+// launches 4.73-4.79 (plain) / 4.61 (nt) / 5.05-5.07 µs (sc1) per step; launches run alone
+// 5.36-5.41 / 5.16 / 4.73 µs. The bench and a training loop run launches back to back.
 typedef int v4i32 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 
 template <int L>
 __device__ __forceinline__ void store_row_p(int32_t* __restrict__ p, const int32_t (&v)[L]) {
-  if constexpr (SCG_BG_STORE != 0 && L % 4 == 0) {
+  if constexpr (L % 4 == 0) {
 #pragma unroll
     for (int c = 0; c < L / 4; ++c) {
       const v4i32 x = {v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]};
-      if constexpr (SCG_BG_STORE == 1) {
-        __builtin_nontemporal_store(x, reinterpret_cast<v4i32*>(p) + c);
-      } else {
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(reinterpret_cast<v4i32*>(p) + c), "v"(x)
-                     : "memory");
-      }
+      __builtin_nontemporal_store(x, reinterpret_cast<v4i32*>(p) + c);
     }
   } else {
     store_row<L>(p, v);
@@ -1107,10 +1093,6 @@ __global__ __launch_bounds__(kBlock) void bg_rollout_lds_kernel(const BgArgs a, 
   }
 }
 
-#ifndef SCG_MODULE_LAUNCH
-#define SCG_MODULE_LAUNCH 1  // 0: unstamped slab launches through hipLaunchKernelGGL (A/B builds)
-#endif
-
 // hipModuleLaunchKernel with the kernel's function handle resolved once per instantiation,
 // skipping the host-stub lookup of hipLaunchKernel on every step: ≈0.5 µs less host time
 // per step (tools/short_region.py, profiles/r02h_short_region.log).
@@ -1197,10 +1179,7 @@ int bg_launch_slab_dm(dim3 grid, hipStream_t s, const SlabLaunch& a, hipEvent_t 
                           a.act, a.out, a.consts, a.key, a.n32, a.wpack, a.week, a.episode, a.demand_fixed);
     return check_launch("bg_step_slab_kernel");
   }
-  if (SCG_MODULE_LAUNCH) return launch_slab_module<L, DM>(grid, s, a);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_slab_kernel<L, DM>), grid, dim3(kBlock), 0, s, a.slab, a.act, a.out,
-                     a.consts, a.key, a.n32, a.wpack, a.week, a.episode, a.demand_fixed);
-  return check_launch("bg_step_slab_kernel");
+  return launch_slab_module<L, DM>(grid, s, a);
 }
 
 template <int L>

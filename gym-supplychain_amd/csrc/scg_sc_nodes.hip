@@ -135,23 +135,6 @@ struct TileWalk {
   }
 };
 
-// Ledger reduce right after each wave's heaps phase (1) or after the last barrier (0, the
-// round-3 placement; A/B in DESIGN §6.7).
-#ifndef SCG_NODES_LED_EARLY
-#define SCG_NODES_LED_EARLY 1
-#endif
-
-#ifndef SCG_NODES_WPE
-#define SCG_NODES_WPE 4
-#endif
-// Streaming (non-temporal) stores for the rows a step writes once and only the next step
-// reads (heap copy-back, stocks, observations): 0 off, 1 the ledger instantiation only, 2
-// every instantiation (sc-2perstage 37.4 -> 36.7 us; the ledger run within noise,
-// profiles/r05j_nodes_nt_ab.log); write-through rather than non-temporal by SCG_NODES_WT
-// (scg_supplychain_nodes.h).
-#ifndef SCG_NODES_NT
-#define SCG_NODES_NT 2
-#endif
 // One tile of 64 envs (tile * 64 ...): the step described at the top, on the kernel arguments
 // `a`, except the step's time, flags and episode, which come from `sp` (sp.t(), sp.flags(),
 // sp.episode(): the batch kernel's launch arguments, read where used as before; the step
@@ -175,8 +158,6 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   using ObsT = typename std::conditional<F64, double, float>::type;
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr bool ledgers = LED;
-  // streaming stores for the heap copy-back and the observation and stock rows (SCG_NODES_NT)
-  constexpr bool kStream = SCG_NODES_NT == 2 || (SCG_NODES_NT == 1 && LED);
   const ScCtx& c = a.c;
   const int NN = c.n_nodes, P = c.P, NP = NN * P, H = c.H;
   const int Ap = c.A | 1, Op = c.O | 1;  // odd row strides: lanes hit distinct banks
@@ -301,7 +282,7 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       int a_i = 0, lt_i = 0;
       for (int p = 0; p < P; ++p) {
         const int hp = i * P + p;
-        sc_nodes_heap<kStream>(c, g, lheap(hp), hsz[hp * 64 + lane], in, ltc, act, sp.t(), i, p, a_i, lt_i, sink);
+        sc_nodes_heap<true>(c, g, lheap(hp), hsz[hp * 64 + lane], in, ltc, act, sp.t(), i, p, a_i, lt_i, sink);
       }
     }
   NSTAMP(3);
@@ -334,23 +315,19 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       if (q1 >= 0) ledger_put(q1, lv1, lk1);
     }
   };
-#if SCG_NODES_LED_EARLY
   // Every slot and mark of an acted env is in place since the act barrier, so each wave
   // reduces its share of the entries as soon as its heaps are done: the slot loads overlap
   // the other waves' heaps and wave 0's reward instead of forming a phase of their own after
-  // the last barrier. A flagged env's slots are written by wave 0's serial walk below, which
-  // then reduces that env's entries itself.
+  // the last barrier (A/B in DESIGN §6.7). A flagged env's slots are written by wave 0's
+  // serial walk below, which then reduces that env's entries itself.
   if (ledgers && live && !flagged) ledger_entries(w, W);
-#endif
 
   // reward
   if (w == 0 && live) {
     double reward;
     if (flagged) {  // untouched by act and heaps: the serial walk on its staged heaps
       reward = sc_nodes_serial<MAXD, !LED>(c, g, lheap, hsz + lane, 64, in, act, sp.t(), sink);
-#if SCG_NODES_LED_EARLY
       if (ledgers) ledger_entries(0, 1);
-#endif
     } else {
       Num total = pyint(0);
       for (int i = 0; i < NN; ++i) total = np_add(total, Num{cost_v[i * 64 + lane], cost_k[i * 64 + lane]});
@@ -369,10 +346,6 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   __syncthreads();
   NSTAMP(7);
 
-#if !SCG_NODES_LED_EARLY
-  if (ledgers && live) ledger_entries(w, W);
-#endif
-
   // out: the tile is this step's observation — obs, or the terminal observation when the
   // env resets now (then wave 0 writes the reset observation to obs), or both
   ObsT* const dst0 = static_cast<ObsT*>(autoreset ? a.term_obs : a.obs);
@@ -380,13 +353,12 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   TileWalk tw(threadIdx.x, blockDim.x, c.O);
   for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw.next()) {
     const ObsT x = obs_t[tw.r * Op + tw.k];
-    // (the step server's rows go to host-mapped memory: plain stores there)
-    if constexpr (kStream && !Step::kKeepsState && SCG_NODES_WT >= 2) {
+    // rows written once per step and read by the next: streaming rather than plain stores
+    // (sc-2perstage 37.4 -> 36.7 us, profiles/r05j_nodes_nt_ab.log), write-through like the heap
+    // copy-back (sc_nodes_heap); the step server's rows go to host-mapped memory: plain stores there
+    if constexpr (!Step::kKeepsState) {
       if (dst0) __hip_atomic_store(&dst0[n0 * c.O + q], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (dst1) __hip_atomic_store(&dst1[n0 * c.O + q], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if constexpr (kStream && !Step::kKeepsState) {
-      if (dst0) __builtin_nontemporal_store(x, &dst0[n0 * c.O + q]);
-      if (dst1) __builtin_nontemporal_store(x, &dst1[n0 * c.O + q]);
     } else {
       if (dst0) dst0[n0 * c.O + q] = x;
       if (dst1) dst1[n0 * c.O + q] = x;
@@ -405,15 +377,9 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   if (live) {  // the stocks of this wave's nodes back, one 64-env row per instruction (the
                // next tile's stage rewrites these rows: the same wave)
     for (int i = w; i < NN; i += W)
-      for (int p = 0; p < P; ++p) {
-        if constexpr (kStream && SCG_NODES_WT >= 2)
-          __hip_atomic_store(&a.stock[(i * P + p) * a.n + n], stk[(i * P + p) * 64 + lane], __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-        else if constexpr (kStream)
-          __builtin_nontemporal_store(stk[(i * P + p) * 64 + lane], &a.stock[(i * P + p) * a.n + n]);
-        else
-          a.stock[(i * P + p) * a.n + n] = stk[(i * P + p) * 64 + lane];
-      }
+      for (int p = 0; p < P; ++p)
+        __hip_atomic_store(&a.stock[(i * P + p) * a.n + n], stk[(i * P + p) * 64 + lane], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
     if (g.overflow) atomicOr(a.err, 1);
   }
   NSTAMP(4);
@@ -425,13 +391,14 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
 
 // Four waves per SIMD (<= 128 VGPRs): two blocks of eight waves per CU, which is also what
 // their LDS allows.
+constexpr int kNodesWavesPerEu = 4;
 // F64: float64 observations; LED: build_info ledgers (a separate instantiation, so the
 // ledger code costs the common run nothing).
 // Persistent: block b steps tiles b, b + gridDim.x, ... (64 envs each); the launch sizes the
 // grid to the blocks the device holds at once, so the second round of tiles needs no new
 // blocks and each block's next tile follows its last without a dispatch.
 template <int MAXD, bool F64, bool LED>
-__global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(SCG_NODES_WPE)))
+__global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(kNodesWavesPerEu)))
 void sc_step_nodes_kernel(const ScArgs a_arg, int W, int E) {
   // the wave index is wave-uniform: said so, node records are read with scalar loads
   const int lane0 = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -625,14 +592,6 @@ int64_t sc_nodes_resident_blocks(int dev, int W, size_t lds) {
   return cache.back().blocks;
 }
 
-#ifndef SCG_NODES_PERSISTENT
-#define SCG_NODES_PERSISTENT 1
-#endif
-
-#ifndef SCG_NODES_LED_PERSISTENT
-#define SCG_NODES_LED_PERSISTENT 0
-#endif
-
 std::atomic<int> g_nodes_max_blocks{0};  // scg_sc_nodes_max_blocks (tests)
 #ifdef SCG_NODES_STAMPS
 constexpr size_t kNodesStaticLds = 8 * 20 * sizeof(unsigned long long);  // s_nodes_stamps
@@ -640,25 +599,31 @@ constexpr size_t kNodesStaticLds = 8 * 20 * sizeof(unsigned long long);  // s_no
 constexpr size_t kNodesStaticLds = 0;
 #endif
 
+// Past 64 KiB of dynamic LDS a kernel is told, once per device, how much it may use.
+template <auto kKernel>
+bool sc_nodes_allow_lds(size_t lds, size_t limit, int& dev) {
+  static std::atomic<bool> raised[64] = {};  // per device
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (lds <= 64 * 1024 || raised[dev].load(std::memory_order_acquire)) return true;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(limit)) != hipSuccess)
+    return false;
+  raised[dev].store(true, std::memory_order_release);
+  return true;
+}
+
 template <int MAXD, bool F64, bool LED>
 int sc_launch_nodes_d(const ScArgs& a, int W, int E, hipStream_t s) {
-  static std::atomic<bool> raised[64] = {};  // per device
   const size_t lds = sc_nodes_lds_bytes(a.c.n_nodes, a.c.P, a.c.H, E, W, a.c.A, a.c.O, F64 ? 8 : 4);
   if (lds > sc_nodes_lds_max()) return fail(SCG_ERR_INVALID, "node-parallel kernel: %zu B of LDS per block", lds);
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (lds > 64 * 1024 && !raised[dev].load(std::memory_order_acquire)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sc_step_nodes_kernel<MAXD, F64, LED>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(sc_nodes_lds_max() - kNodesStaticLds)) != hipSuccess)
-      return fail(SCG_ERR_HIP, "node-parallel kernel: cannot raise its LDS limit");
-    raised[dev].store(true, std::memory_order_release);
-  }
+  if (!sc_nodes_allow_lds<&sc_step_nodes_kernel<MAXD, F64, LED>>(lds, sc_nodes_lds_max() - kNodesStaticLds, dev))
+    return fail(SCG_ERR_HIP, "node-parallel kernel: cannot raise its LDS limit");
   const int64_t tiles = (a.n + 63) / 64;
   int64_t blocks = tiles;
   // the ledger instantiation keeps one block per tile (persistent measured 55.4 -> 56.7 us,
   // profiles/r05f_nodes_persistent_ab.log)
-  if (SCG_NODES_PERSISTENT && (!LED || SCG_NODES_LED_PERSISTENT)) {
+  if (!LED) {
     const int64_t resident = sc_nodes_resident_blocks<MAXD, F64, LED>(dev, W, lds);
     if (resident > 0 && resident < tiles) blocks = resident;
   }
@@ -672,20 +637,18 @@ int sc_launch_nodes_d(const ScArgs& a, int W, int E, hipStream_t s) {
 int sc_launch_nodes(const ScArgs& a, int maxd_bucket, int W, int E, hipStream_t s) {
   if (W < 1 || W > kNodesMaxWaves) return fail(SCG_ERR_INVALID, "node-parallel kernel: %d waves per block", W);
   const int v = (a.obs_f64 ? 1 : 0) | (a.led_v && a.ledp_v ? 2 : 0);
-#define SCG_NODES_CASES(D)                                  \
-  switch (v) {                                              \
-    case 0: return sc_launch_nodes_d<D, false, false>(a, W, E, s); \
-    case 1: return sc_launch_nodes_d<D, true, false>(a, W, E, s);  \
-    case 2: return sc_launch_nodes_d<D, false, true>(a, W, E, s);  \
-    default: return sc_launch_nodes_d<D, true, true>(a, W, E, s);  \
-  }
-  switch (maxd_bucket) {
-    case 2: SCG_NODES_CASES(2)
-    case 4: SCG_NODES_CASES(4)
-    case 8: SCG_NODES_CASES(8)
-    default: return fail(SCG_ERR_INVALID, "node-parallel kernel: nodes ship to at most 8 destinations");
-  }
-#undef SCG_NODES_CASES
+  int rc = SCG_OK;
+  const bool found = sc_dispatch_maxd<8>(maxd_bucket, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    switch (v) {
+      case 0: rc = sc_launch_nodes_d<D, false, false>(a, W, E, s); break;
+      case 1: rc = sc_launch_nodes_d<D, true, false>(a, W, E, s); break;
+      case 2: rc = sc_launch_nodes_d<D, false, true>(a, W, E, s); break;
+      default: rc = sc_launch_nodes_d<D, true, true>(a, W, E, s); break;
+    }
+  });
+  if (!found) return fail(SCG_ERR_INVALID, "node-parallel kernel: nodes ship to at most 8 destinations");
+  return rc;
 }
 
 // The step server's block for a config the batch kernel runs (float64 observations, no
@@ -697,26 +660,17 @@ int sc_launch_nodes_server(const ScArgs& a, int maxd_bucket, int W, int E, hipSt
   const size_t lds = sc_nodes_lds_bytes(a.c.n_nodes, a.c.P, a.c.H, E, W, a.c.A, a.c.O, 8);
   const size_t cap = sc_nodes_lds_max() - kNodesStaticLds - 1024;  // room for the static request words and action row
   if (lds > cap) return fail(SCG_ERR_INVALID, "node-parallel server: %zu B of LDS per block", lds);
-  static std::atomic<bool> raised[3][64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-#define SCG_SERVER_LAUNCH(D, K)                                                                                     \
-  if (lds > 64 * 1024 && !raised[K][dev].load(std::memory_order_acquire)) {                                         \
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sc_nodes_server_kernel<D>),                             \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(cap)) != hipSuccess)       \
-      return fail(SCG_ERR_HIP, "node-parallel server: cannot raise its LDS limit");                                 \
-    raised[K][dev].store(true, std::memory_order_release);                                                          \
-  }                                                                                                                 \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_nodes_server_kernel<D>), dim3(1), dim3(64 * W), lds, s, a, W, E, box,       \
-                     exit_seen, idle_ticks);                                                                        \
-  break;
-  switch (maxd_bucket) {
-    case 2: SCG_SERVER_LAUNCH(2, 0)
-    case 4: SCG_SERVER_LAUNCH(4, 1)
-    case 8: SCG_SERVER_LAUNCH(8, 2)
-    default: return fail(SCG_ERR_INVALID, "node-parallel server: nodes ship to at most 8 destinations");
-  }
-#undef SCG_SERVER_LAUNCH
+  bool raised = true;
+  const bool found = sc_dispatch_maxd<8>(maxd_bucket, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    int dev = 0;
+    raised = sc_nodes_allow_lds<&sc_nodes_server_kernel<D>>(lds, cap, dev);
+    if (raised)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_nodes_server_kernel<D>), dim3(1), dim3(64 * W), lds, s, a, W, E, box,
+                         exit_seen, idle_ticks);
+  });
+  if (!found) return fail(SCG_ERR_INVALID, "node-parallel server: nodes ship to at most 8 destinations");
+  if (!raised) return fail(SCG_ERR_HIP, "node-parallel server: cannot raise its LDS limit");
   return check_launch("sc_nodes_server_kernel");
 }
 

@@ -63,9 +63,6 @@ struct ScAcc {
 #endif
 #endif
 
-#ifndef SCG_SC_LDS_PROBE
-#define SCG_SC_LDS_PROBE 0
-#endif
 #include "scg_supplychain_core.h"
 #include "scg_supplychain_args.h"
 #include "scg_supplychain_level.h"
@@ -135,21 +132,9 @@ __global__ __launch_bounds__(EPB) void sc_step_lds_kernel(const ScArgs a) {
       }
     }
   }
-#if SCG_SC_LDS_PROBE
-  double* lstock = reinterpret_cast<double*>(lsize + NP * EPB);
-  float* lact = reinterpret_cast<float*>(lstock + NP * EPB);
-  if (live) {
-    for (int k = 0; k < NP; ++k) lstock[k * EPB + lane] = a.stock[k * a.n + n];
-    for (int k = 0; k < c.A; ++k) lact[lane * c.A + k] = a.act[n * c.A + k];
-  }
-  const float* act_row = lact + lane * c.A;
-  double* stock_col = lstock + lane;
-  const int64_t stock_stride = EPB;
-#else
   const float* act_row = a.act + n * c.A;
   double* stock_col = a.stock + n;
   const int64_t stock_stride = a.n;
-#endif
   SCG_STAMP(1);
   if (!live) return;  // no block-wide sync below: every lane only touches its own column
   ScEnv e{stock_col, ltk + lane, lval + lane, lsize + lane, stock_stride, EPB,
@@ -187,9 +172,6 @@ __global__ __launch_bounds__(EPB) void sc_step_lds_kernel(const ScArgs a) {
     }
   }
   SCG_STAMP(24);
-#if SCG_SC_LDS_PROBE
-  for (int k = 0; k < NP; ++k) a.stock[k * a.n + n] = lstock[k * EPB + lane];
-#endif
   if (e.overflow) atomicOr(a.err, 1);
   for (int hp = 0; hp < NP; ++hp) {
     const int32_t sz = lsize[hp * EPB + lane];
@@ -207,22 +189,13 @@ __global__ __launch_bounds__(EPB) void sc_step_lds_kernel(const ScArgs a) {
 // is staged in LDS ([slot][lane], lane fastest: conflict free), the
 // shipments go through the env's HBM inbox, the node's observation is written while its
 // heaps are staged. No block-wide barrier: every lane only touches its own LDS column.
-#ifndef SCG_STAGED_WPE
-#define SCG_STAGED_WPE 0  // 0: the compiler's choice
-#endif
 // LED: build_info ledgers kept (a separate instantiation: without it every ledger note,
 // and the per-destination unit sums only ledgers read, compile away).
-// The staged kernel's context re-read per node (KernargCtx): 249 -> 199 VGPRs and a third of
-// the SGPR spill reloads, yet 2.3 % slower on ntom (3.97 -> 4.07 ms, profiles/r05e_*), so off.
-#ifndef SCG_STAGED_KARG_CTX
-#define SCG_STAGED_KARG_CTX 0
-#endif
+// (Re-reading the context per node through the kernel-argument pointer measured 249 -> 199
+// VGPRs and a third of the SGPR spill reloads, yet 2.3 % slower on ntom: 3.97 -> 4.07 ms,
+// profiles/r05e_*.)
 template <int MAXD, bool LED>
-__global__ __launch_bounds__(kScBlock)
-#if SCG_STAGED_WPE
-__attribute__((amdgpu_waves_per_eu(SCG_STAGED_WPE)))
-#endif
-void sc_step_staged_kernel(const ScArgs a) {
+__global__ __launch_bounds__(kScBlock) void sc_step_staged_kernel(const ScArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x;
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kScBlock + lane;
@@ -249,11 +222,7 @@ void sc_step_staged_kernel(const ScArgs a) {
     if (node_obs) main(o, x);
     if (both) extra(o, x);
   };
-#if SCG_STAGED_KARG_CTX
-  const double reward = sc_staged_step_ctx<MAXD, !LED>(KernargCtx{}, g, lh, in, a.act + n * c.A, a.t, sink);
-#else
   const double reward = sc_staged_step<MAXD, !LED>(c, g, lh, in, a.act + n * c.A, a.t, sink);
-#endif
   a.rew[n] = reward;
   if (a.ep_ret) {
     const double r = a.ep_ret[n] + reward;
@@ -541,17 +510,12 @@ bool sc_level_schedule(scg_sc_config* cfg, const scg_sc_node* nodes) {
 // measured 127 us against 70 us per step on MI355X (profiles/r01f_sc_variants.log).
 size_t sc_lds_bytes(const scg_sc_config* cfg, int epb = kScBlock) {
   const size_t NP = static_cast<size_t>(cfg->n_nodes) * cfg->n_products;
-  return epb * NP * (static_cast<size_t>(cfg->heap_capacity) * 12 + 4) +
-         (SCG_SC_LDS_PROBE ? epb * (NP * 8 + static_cast<size_t>(cfg->n_actions) * 4) : 0);
+  return epb * NP * (static_cast<size_t>(cfg->heap_capacity) * 12 + 4);
 }
 
 // Envs per block of the LDS lane kernel for a batch of n: half-full waves when full ones
 // would leave a SIMD with fewer than two (the CU count is read once per device).
-#ifndef SCG_SC_LDS_EPB
-#define SCG_SC_LDS_EPB 0  // 0 = by batch size; 32 or 64 forces one
-#endif
 int sc_lds_epb(int64_t n) {
-  if (SCG_SC_LDS_EPB) return SCG_SC_LDS_EPB;
   static int cus[64] = {0};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
@@ -815,6 +779,7 @@ int scg_sc_step(const scg_sc_config* cfg, scg_sc_state* st, const float* action,
   const dim3 grid = sc_grid(st->n_envs);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t lds = sc_lds_bytes(cfg);
+  const int maxd = sc_maxd_bucket(cfg->max_dests);
   if (cfg->kernel == SCG_SC_KERNEL_LEVEL) {
     if (cfg->layout != SCG_SC_LAYOUT_ENV_MAJOR || cfg->n_levels < 1 || cfg->group < 1 || cfg->group > kScBlock)
       return fail(SCG_ERR_INVALID, "level kernel needs the schedule scg_sc_prepare derives");
@@ -825,65 +790,45 @@ int scg_sc_step(const scg_sc_config* cfg, scg_sc_state* st, const float* action,
     const dim3 lgrid(static_cast<unsigned>((st->n_envs + per_block - 1) / per_block));
     const size_t llds = sc_level_lds_bytes(cfg);
     const int G = cfg->group, IB = cfg->inbox_size;
-#define SCG_LEVEL_LAUNCH(D)                                                                               \
-  if (cfg->level_staged)                                                                                  \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_level_kernel<D, true>), lgrid, dim3(kScBlock), llds, s, a, lv, G, IB); \
-  else                                                                                                    \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_level_kernel<D, false>), lgrid, dim3(kScBlock), llds, s, a, lv, G, IB)
-    switch (sc_maxd_bucket(cfg->max_dests)) {
-      case 2: SCG_LEVEL_LAUNCH(2); break;
-      case 4: SCG_LEVEL_LAUNCH(4); break;
-      case 8: SCG_LEVEL_LAUNCH(8); break;
-      case 16: SCG_LEVEL_LAUNCH(16); break;
-      default: SCG_LEVEL_LAUNCH(32); break;
-    }
-#undef SCG_LEVEL_LAUNCH
+    sc_dispatch_maxd(maxd, [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      if (cfg->level_staged)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_level_kernel<D, true>), lgrid, dim3(kScBlock), llds, s, a, lv, G, IB);
+      else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_level_kernel<D, false>), lgrid, dim3(kScBlock), llds, s, a, lv, G, IB);
+    });
   } else if (cfg->kernel == SCG_SC_KERNEL_NODES && (!st->ledger || st->ledger_part)) {
     if (cfg->layout != SCG_SC_LAYOUT_ENV_FASTEST || cfg->inbox_size < 0)
       return fail(SCG_ERR_INVALID, "node-parallel kernel needs the layout and inbox scg_sc_prepare derives");
-    if (int rc = sc_launch_nodes(a, sc_maxd_bucket(cfg->max_dests), cfg->group, cfg->inbox_size, s)) return rc;
+    if (int rc = sc_launch_nodes(a, maxd, cfg->group, cfg->inbox_size, s)) return rc;
   } else if (cfg->kernel == SCG_SC_KERNEL_STAGED) {
     if (!st->inbox_tk || !st->inbox_val || cfg->inbox_size < 0)
       return fail(SCG_ERR_INVALID, "the staged kernel needs the inbox buffers [inbox_size][N]");
     const size_t slds = sc_staged_lds_bytes(cfg);
-    switch (sc_maxd_bucket(cfg->max_dests)) {
-#define SCG_STAGED_LAUNCH(D)                                                                                   \
-  if (a.led_v)                                                                                                 \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_step_staged_kernel<D, true>), grid, dim3(kScBlock), slds, s, a);    \
-  else                                                                                                         \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_step_staged_kernel<D, false>), grid, dim3(kScBlock), slds, s, a)
-      case 2: SCG_STAGED_LAUNCH(2); break;
-      case 4: SCG_STAGED_LAUNCH(4); break;
-      case 8: SCG_STAGED_LAUNCH(8); break;
-      case 16: SCG_STAGED_LAUNCH(16); break;
-      default: SCG_STAGED_LAUNCH(32); break;
-#undef SCG_STAGED_LAUNCH
-    }
+    sc_dispatch_maxd(maxd, [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      if (a.led_v)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_step_staged_kernel<D, true>), grid, dim3(kScBlock), slds, s, a);
+      else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_step_staged_kernel<D, false>), grid, dim3(kScBlock), slds, s, a);
+    });
   } else if (cfg->layout != SCG_SC_LAYOUT_ENV_FASTEST) {
     return fail(SCG_ERR_INVALID, "lane kernel needs the env-fastest layout");
   } else if (lds <= kScLdsMax) {
     const int epb = sc_lds_epb(st->n_envs);
     const dim3 g2(static_cast<unsigned>((st->n_envs + epb - 1) / epb));
     const size_t l2 = sc_lds_bytes(cfg, epb);
-#define SCG_LDS_LAUNCH(D)                                                                     \
-  if (epb == 32)                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_step_lds_kernel<D, 32>), g2, dim3(32), l2, s, a);   \
-  else                                                                                        \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_step_lds_kernel<D, 64>), g2, dim3(64), l2, s, a)
-    switch (sc_maxd_bucket(cfg->max_dests)) {
-      case 2: SCG_LDS_LAUNCH(2); break;
-      case 4: SCG_LDS_LAUNCH(4); break;
-      case 8: SCG_LDS_LAUNCH(8); break;
-      case 16: SCG_LDS_LAUNCH(16); break;
-      default: SCG_LDS_LAUNCH(32); break;
-    }
-#undef SCG_LDS_LAUNCH
-  } else switch (sc_maxd_bucket(cfg->max_dests)) {
-    case 2: hipLaunchKernelGGL(sc_step_kernel<2>, grid, dim3(kScBlock), 0, s, a); break;
-    case 4: hipLaunchKernelGGL(sc_step_kernel<4>, grid, dim3(kScBlock), 0, s, a); break;
-    case 8: hipLaunchKernelGGL(sc_step_kernel<8>, grid, dim3(kScBlock), 0, s, a); break;
-    case 16: hipLaunchKernelGGL(sc_step_kernel<16>, grid, dim3(kScBlock), 0, s, a); break;
-    default: hipLaunchKernelGGL(sc_step_kernel<32>, grid, dim3(kScBlock), 0, s, a); break;
+    sc_dispatch_maxd(maxd, [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      if (epb == 32)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_step_lds_kernel<D, 32>), g2, dim3(32), l2, s, a);
+      else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_step_lds_kernel<D, 64>), g2, dim3(64), l2, s, a);
+    });
+  } else {
+    sc_dispatch_maxd(maxd, [&](auto d) {
+      hipLaunchKernelGGL(sc_step_kernel<decltype(d)::value>, grid, dim3(kScBlock), 0, s, a);
+    });
   }
   if (int rc = check_launch("sc_step_kernel")) return rc;
   if (autoreset) {

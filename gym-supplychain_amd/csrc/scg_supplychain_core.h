@@ -38,6 +38,19 @@ namespace scg {
 // Compile-time destination bound used for a chain whose widest node ships to d nodes.
 __host__ __device__ constexpr int sc_maxd_bucket(int d) { return d <= 2 ? 2 : d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : 32; }
 
+// The host's way from a bucket to a kernel instantiation: f(std::integral_constant<int, D>)
+// for the bucket's D among 2, 4, 8, 16, 32 (anything else counts as 32). kMax is the widest D
+// the caller instantiates; a wider bucket calls nothing and returns false.
+template <int kMax = 32, int D = 2, class F>
+inline bool sc_dispatch_maxd(int bucket, F&& f) {
+  if (bucket == D || D == 32) {
+    f(std::integral_constant<int, D>{});
+    return true;
+  }
+  if constexpr (D < kMax) return sc_dispatch_maxd<kMax, 2 * D>(bucket, f);
+  return false;
+}
+
 // Node records and threshold/sinusoid tables are read through the constant address space
 // (scg_const.h): their wave-uniform fields become batched scalar loads.
 using ScNode = const SCG_CONST_AS scg_sc_node;
@@ -60,34 +73,7 @@ struct ScCtx {
   ConstTab<double> dbase;
 };
 
-// A wave-uniform pointer the compiler cannot follow across the call (device, kOpaque): loads
-// through it are issued where they are used, not hoisted to a loop's or an unrolled
-// sequence's top with their values held in scalar registers throughout, where a node's many
-// per-destination fields spilled into VGPR lanes. Identity otherwise.
-#ifndef SCG_SC_OPAQUE_DEST
-#define SCG_SC_OPAQUE_DEST 0
-#endif
-template <bool kOpaque, class T>
-__host__ __device__ __forceinline__ T* sc_opaque(T* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (kOpaque) asm volatile("" : "+s"(p));
-#endif
-  return p;
-}
-
-// A wave-uniform integer the compiler cannot follow (device): its multiples and the addresses
-// derived from it are computed where used rather than hoisted out of a loop and held — or
-// spilled — across it. Identity on the host.
-template <class T>
-__host__ __device__ __forceinline__ T sc_opaque_val(T v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+s"(v));
-#endif
-  return v;
-}
-
-// The context of a loop over nodes as a callable (sc_staged_step_ctx): the caller's own. The
-// kernels pass KernargCtx (scg_supplychain_args.h) instead.
+// The context of a loop over nodes as a callable (sc_staged_step_ctx): the caller's own.
 struct HostCtx {
   const ScCtx& c;
   __host__ __device__ __forceinline__ const ScCtx& operator()() const { return c; }
@@ -350,7 +336,6 @@ __host__ __device__ __forceinline__ void sc_push(const ScCtx& c, ScEnv& e, int n
 // destination does; a heap push keeps the loop rolled to bound code size).
 struct DirectPush {
   static constexpr bool kUnroll = false;
-  static constexpr bool kUniformNode = false;
   static constexpr bool kLdsSplit = false;  // see sc_split_scratch
   static constexpr bool kVecActions = false;  // see sc_ship_vals
   static constexpr bool kClearInAct = false;  // see StagedInbox::noship
@@ -721,9 +706,9 @@ __host__ __device__ __forceinline__ Num sc_node_act(const ScCtx& c, ScEnv& e, Wo
           // per-destination array besides the split's output stays live.
           Num leaving = pyint(0), ship_cost = pyint(0), ship_units = pyint(0);
           auto dest_step = [&](int i) {
-            // this destination's node fields, loaded here (Push::kUniformNode: the node is
-            // wave-uniform, so the laundered pointer stays in scalar registers)
-            ScNode& nd = *sc_opaque<Push::kUniformNode && SCG_SC_OPAQUE_DEST>(&c.nodes[ni]);
+            // this destination's node fields through a reference of the step's own, not the
+            // by-reference capture of the act's
+            ScNode& nd = c.nodes[ni];
             Num o;
             if constexpr (Push::kLdsSplit)
               o = cut ? push.scratch_get(rank[i]) : pyint(0);

@@ -28,15 +28,6 @@
 
 #include "scg_supplychain_core.h"
 
-// The node-parallel kernel's streaming stores (the heap copy-back; at 2 also the stock and
-// observation rows of the batch kernel) as write-through stores (sc1: the line leaves the
-// L2 with the store instead of staying dirty until evicted or written back at the launch's
-// end): sc-2perstage 37.2-37.5 -> 35.7-37.0 us, the two-product chain 86-88 -> 82-84 us
-// (profiles/r06t_nodes_wt_ab*.log, r06u_*, r06v_*); 0 keeps the non-temporal stores.
-#ifndef SCG_NODES_WT
-#define SCG_NODES_WT 2
-#endif
-
 namespace scg {
 
 __host__ __device__ __forceinline__ int sc_ctz64(uint64_t m) { return __builtin_ctzll(m); }
@@ -50,7 +41,6 @@ struct NodesInbox {
   int64_t stride;
 
   static constexpr bool kUnroll = true;
-  static constexpr bool kUniformNode = true;  // a wave per node
   static constexpr bool kLdsSplit = false;
   static constexpr bool kVecActions = false;  // actions come from an LDS tile
   static constexpr bool kClearInAct = false;  // cleared before the act
@@ -115,11 +105,8 @@ __host__ __device__ inline bool sc_recv_scan(const HeapView& h, int32_t sz, int 
 // The first chunk does not depend on sz (slots past the size are read and stored, never
 // used), so it is requested together with the size — one memory round for a heap of at
 // most kChunk entries — and a longer heap costs a round per further chunk.
-#ifndef SCG_NODES_STAGE_CHUNK
-#define SCG_NODES_STAGE_CHUNK 4
-#endif
-template <int kChunk = SCG_NODES_STAGE_CHUNK>
 __host__ __device__ __forceinline__ void sc_nodes_copy_heap(const HeapView& gh, const HeapView& lh, int H, int32_t sz) {
+  constexpr int kChunk = 4;
   HeapEntry b[kChunk];
 #pragma unroll
   for (int u = 0; u < kChunk; ++u)
@@ -169,8 +156,12 @@ __host__ __device__ inline Num sc_nodes_act(const ScCtx& c, ScEnv& g, const Node
 // advances them, :243-259) — then its in-transit bins and the copy back to the env's state.
 // The popped sum went into the stock already (sc_nodes_act), unless `receive`: then it is
 // added here (:225-228), as the serial walk below needs.
-// kStream (device): the copy back with non-temporal stores (written once per step, read
-// next step: evict-first in the caches, so they do not push out what this step reads again).
+// kStream (device): the copy back, rows written once per step and read by the next, with
+// write-through stores (sc1: the line leaves the L2 with the store instead of staying dirty
+// until evicted or written back at the launch's end). With the batch kernel's stock and
+// observation rows stored the same way: sc-2perstage 37.2-37.5 -> 35.7-37.0 us against
+// non-temporal stores, the two-product chain 86-88 -> 82-84 us (profiles/r06t_nodes_wt_ab*.log,
+// r06u_*, r06v_*).
 template <bool kStream = false, class Sink>
 __host__ __device__ inline void sc_nodes_heap(const ScCtx& c, ScEnv& g, const HeapView& lh, int32_t& sz,
                                               const NodesInbox& in, WordCache& ltc, const float* act, int t, int i,
@@ -204,15 +195,8 @@ __host__ __device__ inline void sc_nodes_heap(const ScCtx& c, ScEnv& g, const He
   sc_observe_bins(c, lh, sz, t, i, p, out, [&](int k, const HeapEntry& e) {  // copy back
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (kStream) {
-#if SCG_NODES_WT
-      // write-through (sc1): the line leaves the L2 now instead of staying dirty for the
-      // kernel's end-of-launch write-back
       __hip_atomic_store(&gh.tk[k * gh.stride], e.tk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&gh.val[k * gh.stride], e.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-      __builtin_nontemporal_store(e.tk, &gh.tk[k * gh.stride]);
-      __builtin_nontemporal_store(e.v, &gh.val[k * gh.stride]);
-#endif
       return;
     }
 #endif

@@ -59,9 +59,6 @@ struct HeapView8 {
 };
 
 // Shipments into the destinations' inbox entries; entry q of this env at [q * stride].
-#ifndef SCG_STAGED_OPAQUE_STRIDE
-#define SCG_STAGED_OPAQUE_STRIDE 0
-#endif
 struct StagedInbox {
   uint8_t* tk;  // (time - t) << 3 | kind, kStagedNone = no shipment
   double* val;
@@ -70,16 +67,12 @@ struct StagedInbox {
   int32_t t;      // the step's time: shipments are stored relative to it
 
   static constexpr bool kUnroll = true;  // a store per destination
-  static constexpr bool kUniformNode = true;  // one lane per env, nodes in turn: the node is wave-uniform
   static constexpr bool kLdsSplit = true;
   static constexpr bool kVecActions = true;  // the env's action row in HBM
-#ifndef SCG_STAGED_NOSHIP
-#define SCG_STAGED_NOSHIP 1
-#endif
   // Entries the act does not ship to are marked empty by the act itself (noship /
   // noship_all: one store per destination and product in all), instead of a clear of the
   // node's every entry before it acts followed by the shipments' stores over most of them.
-  static constexpr bool kClearInAct = SCG_STAGED_NOSHIP != 0;
+  static constexpr bool kClearInAct = true;
 #ifndef SCG_STAGED_SHIP_BITS
 #define SCG_STAGED_SHIP_BITS 0
 #endif
@@ -102,7 +95,7 @@ struct StagedInbox {
   }
   __host__ __device__ __forceinline__ void ship(const ScCtx& c, ScEnv&, int src, int d, int /*dest*/, int p,
                                                 int32_t time, Num amount) const {
-    ScNode& nd = *sc_opaque<SCG_SC_OPAQUE_DEST != 0>(&c.nodes[src]);
+    ScNode& nd = c.nodes[src];
     const int64_t q = nd.in_slot[d] + static_cast<int64_t>(p) * nd.in_stride[d];
     tk[q * stride] = static_cast<uint8_t>(he_pack(time - t, amount.k));
     val[q * stride] = amount.v;
@@ -115,13 +108,6 @@ struct StagedInbox {
     ScNode& nd = c.nodes[src];
     for (int d = 0; d < nd.n_dests; ++d)
       tk[(nd.in_slot[d] + static_cast<int64_t>(p) * nd.in_stride[d]) * stride] = kStagedNone;
-  }
-  // node src ships nothing this step unless its act writes an entry
-  __host__ __device__ __forceinline__ void clear(const ScCtx& c, int src) const {
-    ScNode& nd = c.nodes[src];
-    for (int d = 0; d < nd.n_dests; ++d)
-      for (int p = 0; p < c.P; ++p)
-        tk[(nd.in_slot[d] + static_cast<int64_t>(p) * nd.in_stride[d]) * stride] = kStagedNone;
   }
 };
 
@@ -145,13 +131,7 @@ __host__ __device__ inline void sc_staged_heap(const ScCtx& c, ScEnv& g, const H
   // heap size, the stock and the first inbox chunk are requested together up front.
   // (kChunk = 8 pushed the kernel to 256 VGPRs, one wave per SIMD, and ran slower.)
   constexpr int kChunk = 4;
-#ifndef SCG_STAGED_HCHUNK
-#define SCG_STAGED_HCHUNK 8
-#endif
-  constexpr int kHeapChunk = SCG_STAGED_HCHUNK;  // heap slots per memory round
-#ifndef SCG_STAGED_PLAIN
-#define SCG_STAGED_PLAIN 1
-#endif
+  constexpr int kHeapChunk = 8;  // heap slots per memory round
   const int64_t q0 = nd.in_base + static_cast<int64_t>(p) * nd.in_deg;
   const int32_t t0 = t << 3;  // an absolute time<<3|kind minus t0 is the relative one
   HeapEntry ib[kChunk];
@@ -202,13 +182,13 @@ __host__ __device__ inline void sc_staged_heap(const ScCtx& c, ScEnv& g, const H
   SCG_ACC(1);
   // the pops, the phase's longest part, compare the doubles when no lane of the wave holds
   // a Python int or float amount (a wave-uniform choice, so no lane runs both bodies)
-#if SCG_STAGED_PLAIN && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   if (__all(plain))
     st = st0 + sc_receive<true>(lh, sz, 0);
   else
     st = st0 + sc_receive(lh, sz, 0);
 #else
-  st = st0 + (SCG_STAGED_PLAIN && plain ? sc_receive<true>(lh, sz, 0) : sc_receive(lh, sz, 0));
+  st = st0 + (plain ? sc_receive<true>(lh, sz, 0) : sc_receive(lh, sz, 0));
 #endif
   SCG_ACC(2);
   if (nd.n_supply > 0 && nd.supply_capacity[p] > 0) {
@@ -234,9 +214,9 @@ __host__ __device__ inline void sc_staged_heap(const ScCtx& c, ScEnv& g, const H
 // shares. out(o, x) receives the node observation elements (the caller adds the demand and
 // time-to-go ones). Returns the reward. (Staging the node's stocks in LDS as well measured
 // no faster on MI355X: stock accesses are few and cache-resident.)
-// ctx() gives the launch-uniform context; each node's iteration asks for it again (the
-// kernel's KernargCtx re-reads it through a pointer the compiler cannot see across
-// iterations, so nothing derived from it is held in registers across the node loop).
+// ctx() gives the launch-uniform context; each node's iteration asks for it again. (With the
+// collapse of this indirection into a plain `const ScCtx&` parameter the compiler emits other
+// code for every sc_step_staged_kernel instantiation, so it stays.)
 template <int MAXD, bool kKindPaths = false, class CtxFn, class Sink>
 __host__ __device__ inline double sc_staged_step_ctx(const CtxFn& ctx, ScEnv& g, const HeapView8& lh,
                                                      const StagedInbox& in, const float* act, int t, Sink& out) {
@@ -249,18 +229,9 @@ __host__ __device__ inline double sc_staged_step_ctx(const CtxFn& ctx, ScEnv& g,
   const int NN = ctx().n_nodes;
   for (int i = 0; i < NN; ++i) {
     const ScCtx& c = ctx();
-    ScNode& nd = c.nodes[i];
-    // the batch strides (uniform: the env-fastest layout) made opaque per node, so their many
-    // multiples (slot and entry offsets) are formed where used, not held across the loop
     StagedInbox inl = in;
-#if SCG_STAGED_OPAQUE_STRIDE
-    g.stride = sc_opaque_val(g.stride);
-    g.hstride = sc_opaque_val(g.hstride);
-    inl.stride = sc_opaque_val(inl.stride);
-#endif
     int a_i = 0, lt_i = 0;
     for (int p = 0; p < c.P; ++p) sc_staged_heap(c, g, lh, inl, ltc, act, t, i, p, a_i, lt_i, out, scg_acc_);
-    if (!StagedInbox::kClearInAct && !nd.last_level) inl.clear(c, i);
     SCG_ACC(7);
     total = np_add(total, sc_node_act<MAXD, StagedInbox, true, kKindPaths>(c, g, ltc, dmc, i, act, t, inl));
     SCG_ACC(5);

@@ -310,8 +310,8 @@ def test_nodes_kernel_persistent_tiles_equal_lane_kernel(scenario, kw, n_envs, m
     products with ledgers, and every env on the serial walk — identical obs, rewards,
     returns, stocks, heaps and ledgers. The cap applies to the ledger instantiation too, so
     with max_blocks 2 or 3 this test deliberately runs its tile loop over several tiles per
-    block, which production never does (that instantiation keeps one block per tile,
-    SCG_NODES_LED_PERSISTENT=0); max_blocks 0 is the production grid."""
+    block, which production never does (the ledger instantiation keeps one block per tile);
+    max_blocks 0 is the production grid."""
     import gym_supplychain_amd as gsa
     from gym_supplychain_amd import _native as nat
     kw = dict(kw)
