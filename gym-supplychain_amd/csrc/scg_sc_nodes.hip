@@ -28,6 +28,9 @@
 // node after node in the reference's order (sc_nodes_serial). Observations and actions go
 // through LDS tiles so HBM sees whole rows; the state pointers stay the batch's base
 // pointers (ScEnv soff/hoff) so they live in SGPRs.
+// The same tile code runs under two more drivers: the rollout kernel (a step loop inside the
+// tile loop, the state in LDS between a launch's steps) and the step server (one resident
+// block serving a drop-in env's steps).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -142,14 +145,54 @@ struct TileWalk {
 // state: the step server's block stepped this env last and its LDS still holds the stocks,
 // sizes, heaps and episode return that step left. lane is the thread's lane, opaque to the
 // compiler; w the wave index.
+// The step's outputs go where the policy says as well (sp.obs<T>(a), sp.rew(a), sp.term_obs(a):
+// the launch arguments' buffers for the batch kernel and the step server, step k's slices of
+// them for the rollout kernel), and sp.write_back() says whether the step leaves the env's
+// heaps, sizes, stocks and episode return in HBM (always, but for the rollout kernel's steps
+// whose successor finds them in LDS). kStreamOut: observation rows with write-through stores
+// (device memory) rather than plain ones (the step server's host-mapped rows). kObsOptional:
+// sp.obs may be null (a step whose observation nobody asked for).
 struct NodesLaunchStep {  // the batch kernel: the step fields of the launch arguments
   static constexpr bool kKeepsState = false;
+  static constexpr bool kStreamOut = true;
+  static constexpr bool kObsOptional = false;
   const ScArgs& a;
   __device__ __forceinline__ int t() const { return a.t; }
   __device__ __forceinline__ int flags() const { return a.flags; }
   __device__ __forceinline__ uint32_t episode() const { return a.episode; }
   __device__ __forceinline__ const float* act(const ScArgs& x) const { return x.act; }
   __device__ __forceinline__ bool keep_state() const { return false; }
+  template <class T>
+  __device__ __forceinline__ T* obs(const ScArgs& x) const { return static_cast<T*>(x.obs); }
+  __device__ __forceinline__ void* term_obs(const ScArgs& x) const { return x.term_obs; }
+  __device__ __forceinline__ double* rew(const ScArgs& x) const { return x.rew; }
+  __device__ __forceinline__ bool write_back() const { return true; }
+};
+
+// Step k of a rollout launch (sc_rollout_nodes_kernel): its time, episode and flags, counted
+// on from the launch's first step by the kernel's step loop (wave-uniform: SGPRs), and the
+// k-th slices of the launch's action, observation and reward buffers.
+struct NodesRolloutStep {
+  static constexpr bool kKeepsState = true;  // the episode return travels in LDS (ret0)
+  static constexpr bool kStreamOut = true;
+  static constexpr bool kObsOptional = true;
+  int32_t t_, flags_;
+  uint32_t episode_;
+  int32_t k_;        // the step's index in the launch
+  int32_t obs_row_;  // the row block of the observation buffer it writes, -1: none
+  bool keep_, write_back_;
+  __device__ __forceinline__ int t() const { return t_; }
+  __device__ __forceinline__ int flags() const { return flags_; }
+  __device__ __forceinline__ uint32_t episode() const { return episode_; }
+  __device__ __forceinline__ const float* act(const ScArgs& x) const { return x.act + static_cast<int64_t>(k_) * x.n * x.c.A; }
+  __device__ __forceinline__ bool keep_state() const { return keep_; }
+  template <class T>
+  __device__ __forceinline__ T* obs(const ScArgs& x) const {
+    return obs_row_ < 0 ? nullptr : static_cast<T*>(x.obs) + static_cast<int64_t>(obs_row_) * x.n * x.c.O;
+  }
+  __device__ __forceinline__ void* term_obs(const ScArgs& x) const { return x.term_obs; }
+  __device__ __forceinline__ double* rew(const ScArgs& x) const { return x.rew + static_cast<int64_t>(k_) * x.n; }
+  __device__ __forceinline__ bool write_back() const { return write_back_; }
 };
 
 template <int MAXD, bool F64, bool LED, class Step>
@@ -282,7 +325,8 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       int a_i = 0, lt_i = 0;
       for (int p = 0; p < P; ++p) {
         const int hp = i * P + p;
-        sc_nodes_heap<true>(c, g, lheap(hp), hsz[hp * 64 + lane], in, ltc, act, sp.t(), i, p, a_i, lt_i, sink);
+        sc_nodes_heap<true>(c, g, lheap(hp), hsz[hp * 64 + lane], in, ltc, act, sp.t(), i, p, a_i, lt_i, sink, false,
+                            sp.write_back());
       }
     }
   NSTAMP(3);
@@ -326,18 +370,18 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   if (w == 0 && live) {
     double reward;
     if (flagged) {  // untouched by act and heaps: the serial walk on its staged heaps
-      reward = sc_nodes_serial<MAXD, !LED>(c, g, lheap, hsz + lane, 64, in, act, sp.t(), sink);
+      reward = sc_nodes_serial<MAXD, !LED>(c, g, lheap, hsz + lane, 64, in, act, sp.t(), sink, sp.write_back());
       if (ledgers) ledger_entries(0, 1);
     } else {
       Num total = pyint(0);
       for (int i = 0; i < NN; ++i) total = np_add(total, Num{cost_v[i * 64 + lane], cost_k[i * 64 + lane]});
       reward = np_neg(total).v;
     }
-    a.rew[n] = reward;
+    sp.rew(a)[n] = reward;
     if (a.ep_ret) {
       const double r = ret0[lane] + reward;  // episode_rewards += current_reward (:739)
       if (terminal && a.final_ret) a.final_ret[n] = r;
-      a.ep_ret[n] = autoreset ? 0.0 : r;
+      if (sp.write_back()) a.ep_ret[n] = autoreset ? 0.0 : r;
       if constexpr (Step::kKeepsState) ret0[lane] = autoreset ? 0.0 : r;  // the next request's
     }
     for (int k = 0; k < c.R * c.P; ++k) sc_observe_demand(c, g, sp.t(), k, sink);  // (:771)
@@ -348,15 +392,15 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
 
   // out: the tile is this step's observation — obs, or the terminal observation when the
   // env resets now (then wave 0 writes the reset observation to obs), or both
-  ObsT* const dst0 = static_cast<ObsT*>(autoreset ? a.term_obs : a.obs);
-  ObsT* const dst1 = (terminal && !autoreset) ? static_cast<ObsT*>(a.term_obs) : nullptr;
+  ObsT* const dst0 = autoreset ? static_cast<ObsT*>(sp.term_obs(a)) : sp.template obs<ObsT>(a);
+  ObsT* const dst1 = (terminal && !autoreset) ? static_cast<ObsT*>(sp.term_obs(a)) : nullptr;
   TileWalk tw(threadIdx.x, blockDim.x, c.O);
   for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw.next()) {
     const ObsT x = obs_t[tw.r * Op + tw.k];
     // rows written once per step and read by the next: streaming rather than plain stores
     // (sc-2perstage 37.4 -> 36.7 us, profiles/r05j_nodes_nt_ab.log), write-through like the heap
     // copy-back (sc_nodes_heap); the step server's rows go to host-mapped memory: plain stores there
-    if constexpr (!Step::kKeepsState) {
+    if constexpr (Step::kStreamOut) {
       if (dst0) __hip_atomic_store(&dst0[n0 * c.O + q], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (dst1) __hip_atomic_store(&dst1[n0 * c.O + q], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
@@ -369,24 +413,47 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       g.episode = sp.episode() + 1;
       g.led_v = nullptr;   // the ledger was restarted above
       sc_reset_env(c, g);  // heaps in HBM, stocks in the LDS copy
-      ObsRow out{a.obs, n * c.O, F64 ? 1 : 0};
-      sc_observe(c, g, 0, out);
+      ObsT* const robs = sp.template obs<ObsT>(a);
+      if (!Step::kObsOptional || robs) {
+        ObsRow out{robs, n * c.O, F64 ? 1 : 0};
+        sc_observe(c, g, 0, out);
+      }
+      // The rollout kernel's next step stages the new episode's heap and size rows from HBM,
+      // every wave its own nodes' — rows wave 0 wrote just above with plain stores. The
+      // barrier below orders them: __syncthreads() is a workgroup-scope release fence (this
+      // wave waits until its stores have completed), the barrier, and a workgroup-scope
+      // acquire fence. No cache action is needed on top: the waves of a workgroup run on one
+      // CU (the kernels are not built for threadgroup-split mode) and share its vector L1,
+      // through which both the stores (write-through) and the loads go — the LLVM AMDGPU
+      // memory model for gfx90a/gfx942 ("no special action is required for coherence between
+      // wavefronts in the same work-group" outside tgsplit mode). The explicit wait keeps the
+      // stores' completion from depending on what the fence lowers to.
+      if constexpr (Step::kObsOptional) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
   }
   if (live) {  // the stocks of this wave's nodes back, one 64-env row per instruction (the
                // next tile's stage rewrites these rows: the same wave)
-    for (int i = w; i < NN; i += W)
-      for (int p = 0; p < P; ++p)
-        __hip_atomic_store(&a.stock[(i * P + p) * a.n + n], stk[(i * P + p) * 64 + lane], __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+    if (sp.write_back())
+      for (int i = w; i < NN; i += W)
+        for (int p = 0; p < P; ++p)
+          __hip_atomic_store(&a.stock[(i * P + p) * a.n + n], stk[(i * P + p) * 64 + lane], __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
     if (g.overflow) atomicOr(a.err, 1);
   }
   NSTAMP(4);
 #undef NACC
   // the next tile's stage rewrites the action tile, ret0 and, per wave, only the stock, size
   // and heap rows of its own nodes (whose stocks it copied back just above); the rows other
-  // waves read (the observation tile) are next written after that tile's first barrier
+  // waves read (the observation tile) are next written after that tile's first barrier.
+  // The same holds when the next "tile" is these envs one step later (the step server, the
+  // rollout kernel): every read of the action tile, the inbox, the cost rows and — by wave
+  // 0's serial walk and reset — of other waves' heap, size and stock rows lies before this
+  // step's last barrier, which every thread has passed before it stages the next step; a
+  // kept step's stage writes only the wave's own released sums and flag row and the action
+  // tile, a reloading one also its own stock, size and heap rows (the stock rows it stored
+  // just above itself: same thread, same address, program order) and wave 0 ret0, which only
+  // wave 0 reads.
 }
 
 // Four waves per SIMD (<= 128 VGPRs): two blocks of eight waves per CU, which is also what
@@ -420,6 +487,64 @@ void sc_step_nodes_kernel(const ScArgs a_arg, int W, int E) {
   }
 }
 
+// ---- rollout: K steps per launch, the state in LDS between them (scg_sc_rollout) ----------
+// The batch kernel's block, LDS layout and persistent tile loop, with a step loop inside: a
+// block takes a tile of 64 envs through all K steps of the launch before its next tile, and
+// between two steps the tile's stocks, heap sizes, heaps and episode returns stay in LDS
+// (keep_state(), as the step server's between two requests). Step k of the launch reads the
+// action rows [k][N][A] and writes reward row [k][N] and, by obs_mode, observation rows
+// [k][N][O] (0), the one [N][O] buffer at the launch's last step only (1), or none (2).
+// Launch arguments: a.t the first step's time (1..T), a.episode its episode, a.flags bit1
+// "reset at every terminal step" (else the launcher lets no step follow a terminal one),
+// bit2 the serial walk. Step k's time, episode and flags are counted on from those: all
+// wave-uniform, in SGPRs.
+// HBM sees the state only where a later reader needs it there (write_back()): at the
+// launch's last step, and at an auto-reset step — sc_reset_env writes the new episode's
+// heaps and sizes to HBM (wave 0, every node's), not to the other waves' LDS rows, so the
+// step after a reset stages from HBM like a launch's first (keep_state() false; the barrier
+// that orders it: the end of sc_nodes_tile). A kept step neither loads nor stores state:
+// its memory rounds are the action rows in, the reward and observation rows out.
+template <int MAXD, bool F64>
+__global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(kNodesWavesPerEu)))
+void sc_rollout_nodes_kernel(const ScArgs a_arg, int W, int E, int K, int obs_mode) {
+  const int lane0 = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t n_tiles = (a_arg.n + 63) / 64;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    int32_t t = a_arg.t;
+    uint32_t episode = a_arg.episode;
+    bool keep = false;  // the tile's first step in the launch stages from HBM
+    for (int k = 0; k < K; ++k) {
+      // lane and launch arguments opaque per step, as per tile in the batch kernel: nothing
+      // derived from them is carried from one step's code into the next
+      int lane;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane0));
+      typedef const __attribute__((address_space(4))) ScArgs* KArgPtr;
+      KArgPtr ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(ap));
+      const ScArgs& a = *(const ScArgs*)ap;
+      const bool terminal = t == a.c.T;
+      const bool autoreset = terminal && (a.flags & 2);
+      const bool last = k == K - 1;
+      NodesRolloutStep sp;
+      sp.t_ = t;
+      sp.flags_ = (terminal ? 1 : 0) | (autoreset ? 2 : 0) | (a.flags & 4);
+      sp.episode_ = episode;
+      sp.k_ = k;
+      sp.obs_row_ = obs_mode == 0 ? k : (obs_mode == 1 && last) ? 0 : -1;
+      sp.keep_ = keep;
+      sp.write_back_ = last || autoreset;
+      sc_nodes_tile<MAXD, F64, false>(a, tile, lane, w, W, E, sp);
+      keep = !autoreset;
+      if (autoreset) {
+        t = 1;
+        ++episode;
+      } else {
+        ++t;
+      }
+    }
+  }
+}
+
 // ---- step server for the drop-in SupplyChainEnv (include/scgpu.h scg_sc_server_*) --------
 // One block of the batch kernel's shape, resident: wave 0 polls the mailbox's request lines
 // (the request and the inline action row, lanes 0-31, system scope, with the exit word) and
@@ -444,7 +569,14 @@ __shared__ unsigned long long s_srv_seen;
 #endif
 struct NodesServerStep {
   static constexpr bool kKeepsState = true;
+  static constexpr bool kStreamOut = false;  // host-mapped rows
+  static constexpr bool kObsOptional = false;
   bool inline_act;
+  template <class T>
+  __device__ __forceinline__ T* obs(const ScArgs& x) const { return static_cast<T*>(x.obs); }
+  __device__ __forceinline__ void* term_obs(const ScArgs& x) const { return x.term_obs; }
+  __device__ __forceinline__ double* rew(const ScArgs& x) const { return x.rew; }
+  __device__ __forceinline__ bool write_back() const { return true; }
   __device__ __forceinline__ int t() const { return s_srv_req[0]; }
   __device__ __forceinline__ int flags() const { return s_srv_req[1]; }
   __device__ __forceinline__ uint32_t episode() const { return static_cast<uint32_t>(s_srv_req[2]); }
@@ -569,9 +701,9 @@ size_t sc_nodes_lds_max() {
   return v;
 }
 
-// Blocks the device holds at once for this instantiation (occupancy x CUs), asked once per
-// device and shape; the persistent grid is that many blocks, or one per tile when fewer.
-template <int MAXD, bool F64, bool LED>
+// Blocks the device holds at once for this kernel instantiation (occupancy x CUs), asked once
+// per device and shape; the persistent grid is that many blocks, or one per tile when fewer.
+template <auto kKernel>
 int64_t sc_nodes_resident_blocks(int dev, int W, size_t lds) {
   struct Entry {
     int dev, W;
@@ -584,8 +716,7 @@ int64_t sc_nodes_resident_blocks(int dev, int W, size_t lds) {
   for (const Entry& e : cache)
     if (e.dev == dev && e.W == W && e.lds == lds) return e.blocks;
   int per_cu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&sc_step_nodes_kernel<MAXD, F64, LED>),
-                                                   64 * W, lds) != hipSuccess ||
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kKernel), 64 * W, lds) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1)
     return 0;  // unknown: one block per tile
   cache.push_back(Entry{dev, W, lds, static_cast<int64_t>(per_cu) * cus});
@@ -624,7 +755,7 @@ int sc_launch_nodes_d(const ScArgs& a, int W, int E, hipStream_t s) {
   // the ledger instantiation keeps one block per tile (persistent measured 55.4 -> 56.7 us,
   // profiles/r05f_nodes_persistent_ab.log)
   if (!LED) {
-    const int64_t resident = sc_nodes_resident_blocks<MAXD, F64, LED>(dev, W, lds);
+    const int64_t resident = sc_nodes_resident_blocks<&sc_step_nodes_kernel<MAXD, F64, LED>>(dev, W, lds);
     if (resident > 0 && resident < tiles) blocks = resident;
   }
   const int cap = g_nodes_max_blocks.load(std::memory_order_relaxed);
@@ -648,6 +779,41 @@ int sc_launch_nodes(const ScArgs& a, int maxd_bucket, int W, int E, hipStream_t 
     }
   });
   if (!found) return fail(SCG_ERR_INVALID, "node-parallel kernel: nodes ship to at most 8 destinations");
+  return rc;
+}
+
+// K steps of every env in one launch (sc_rollout_nodes_kernel): the batch kernel's block, LDS
+// and persistent grid. a.t / a.episode / a.flags describe the launch's first step; obs_mode as
+// the kernel's. No ledgers.
+template <int MAXD, bool F64>
+int sc_launch_nodes_rollout_d(const ScArgs& a, int W, int E, int K, int obs_mode, hipStream_t s) {
+  const size_t lds = sc_nodes_lds_bytes(a.c.n_nodes, a.c.P, a.c.H, E, W, a.c.A, a.c.O, F64 ? 8 : 4);
+  if (lds > sc_nodes_lds_max()) return fail(SCG_ERR_INVALID, "node-parallel rollout: %zu B of LDS per block", lds);
+  int dev = 0;
+  if (!sc_nodes_allow_lds<&sc_rollout_nodes_kernel<MAXD, F64>>(lds, sc_nodes_lds_max() - kNodesStaticLds, dev))
+    return fail(SCG_ERR_HIP, "node-parallel rollout: cannot raise its LDS limit");
+  const int64_t tiles = (a.n + 63) / 64;
+  int64_t blocks = tiles;
+  const int64_t resident = sc_nodes_resident_blocks<&sc_rollout_nodes_kernel<MAXD, F64>>(dev, W, lds);
+  if (resident > 0 && resident < tiles) blocks = resident;
+  const int cap = g_nodes_max_blocks.load(std::memory_order_relaxed);
+  if (cap > 0 && cap < blocks) blocks = cap;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_rollout_nodes_kernel<MAXD, F64>), dim3(static_cast<unsigned>(blocks)),
+                     dim3(64 * W), lds, s, a, W, E, K, obs_mode);
+  return check_launch("sc_rollout_nodes_kernel");
+}
+
+int sc_launch_nodes_rollout(const ScArgs& a, int maxd_bucket, int W, int E, int K, int obs_mode, hipStream_t s) {
+  if (W < 1 || W > kNodesMaxWaves) return fail(SCG_ERR_INVALID, "node-parallel rollout: %d waves per block", W);
+  if (a.led_v) return fail(SCG_ERR_INVALID, "node-parallel rollout: no ledgers");
+  if (K < 1 || obs_mode < 0 || obs_mode > 2) return fail(SCG_ERR_INVALID, "node-parallel rollout: steps / observation mode");
+  int rc = SCG_OK;
+  const bool found = sc_dispatch_maxd<8>(maxd_bucket, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    rc = a.obs_f64 ? sc_launch_nodes_rollout_d<D, true>(a, W, E, K, obs_mode, s)
+                   : sc_launch_nodes_rollout_d<D, false>(a, W, E, K, obs_mode, s);
+  });
+  if (!found) return fail(SCG_ERR_INVALID, "node-parallel rollout: nodes ship to at most 8 destinations");
   return rc;
 }
 

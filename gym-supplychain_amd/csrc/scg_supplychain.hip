@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -79,6 +80,7 @@ size_t sc_nodes_lds_max();
 int sc_launch_nodes(const ScArgs& a, int maxd_bucket, int W, int E, hipStream_t s);
 int sc_launch_nodes_server(const ScArgs& a, int maxd_bucket, int W, int E, hipStream_t s, scg_sc_server_box* box,
                            uint32_t exit_seen, uint32_t idle_ticks);
+int sc_launch_nodes_rollout(const ScArgs& a, int maxd_bucket, int W, int E, int K, int obs_mode, hipStream_t s);
 
 __global__ __launch_bounds__(kScBlock) void sc_reset_kernel(const ScArgs a) {
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kScBlock + threadIdx.x;
@@ -838,6 +840,78 @@ int scg_sc_step(const scg_sc_config* cfg, scg_sc_state* st, const float* action,
     st->time_step = t;
   }
   if (done) *done = terminal ? 1 : 0;
+  return SCG_OK;
+}
+
+// Steps per launch of the fused rollout (scg_sc_rollout_chunk, tests); 0: SCG_SC_ROLLOUT_MAX.
+static std::atomic<int> g_sc_rollout_chunk{0};
+
+int scg_sc_rollout_chunk(int32_t steps) {
+  return g_sc_rollout_chunk.exchange(steps < 0 ? 0 : steps > SCG_SC_ROLLOUT_MAX ? SCG_SC_ROLLOUT_MAX : steps);
+}
+
+int scg_sc_rollout(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const float* actions, void* obs,
+                   double* rewards, void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
+  if (int rc = sc_check(cfg, st)) return rc;
+  if (n_steps < 1) return fail(SCG_ERR_INVALID, "rollout of %d steps", n_steps);
+  if (!actions || !obs || !rewards) return fail(SCG_ERR_INVALID, "actions/obs/rewards buffers are required");
+  if (flags & ~(SCG_BG_AUTORESET | SCG_SC_SERIAL | SCG_SC_LAST_OBS)) return fail(SCG_ERR_INVALID, "unknown rollout flags");
+  if (st->time_step < 0) return fail(SCG_ERR_NOT_RESET, "rollout() before reset()");
+  const int T = cfg->total_time_steps;
+  if (st->time_step >= T) return fail(SCG_ERR_PAST_HORIZON, "rollout() after the terminal step %d", T);
+  const bool reset = flags & SCG_BG_AUTORESET;
+  if (!reset && static_cast<int64_t>(st->time_step) + n_steps > T)
+    return fail(SCG_ERR_PAST_HORIZON, "rollout() of %d steps from step %d passes the terminal step %d", n_steps,
+                st->time_step, T);
+  const bool last_only = flags & SCG_SC_LAST_OBS;
+  const int64_t N = st->n_envs;
+  const size_t obs_row = static_cast<size_t>(N) * cfg->n_obs * (cfg->obs_f64 ? 8 : 4);
+  int32_t crossed = 0;
+  if (cfg->kernel != SCG_SC_KERNEL_NODES || st->ledger) {  // every other config: one step launch per step
+    const uint32_t step_flags = flags & (SCG_BG_AUTORESET | SCG_SC_SERIAL);
+    for (int32_t k = 0; k < n_steps; ++k) {
+      int32_t done = 0;
+      void* o = last_only ? obs : static_cast<unsigned char*>(obs) + obs_row * k;
+      if (int rc = scg_sc_step(cfg, st, actions + static_cast<int64_t>(k) * N * cfg->n_actions, o, rewards + k * N,
+                               terminal_obs, step_flags, &done, stream))
+        return rc;
+      crossed += done;
+    }
+    if (n_done) *n_done = crossed;
+    return SCG_OK;
+  }
+  if (cfg->layout != SCG_SC_LAYOUT_ENV_FASTEST || cfg->inbox_size < 0)
+    return fail(SCG_ERR_INVALID, "node-parallel kernel needs the layout and inbox scg_sc_prepare derives");
+  const int maxd = sc_maxd_bucket(cfg->max_dests);
+  const int hook = g_sc_rollout_chunk.load(std::memory_order_relaxed);
+  const int chunk = hook > 0 ? hook : SCG_SC_ROLLOUT_MAX;
+  // launches of at most `chunk` steps; each ends with the state written back, so the next
+  // one's first step stages from HBM like any launch's, and st is advanced launch by launch
+  for (int32_t k0 = 0; k0 < n_steps; k0 += chunk) {
+    const int32_t kc = std::min<int32_t>(chunk, n_steps - k0);
+    const bool final = k0 + kc == n_steps;
+    ScArgs a = sc_args(cfg, st);
+    a.act = actions + static_cast<int64_t>(k0) * N * cfg->n_actions;
+    a.obs = last_only ? obs : static_cast<unsigned char*>(obs) + obs_row * k0;
+    a.term_obs = terminal_obs;
+    a.rew = rewards + static_cast<int64_t>(k0) * N;
+    a.t = st->time_step + 1;
+    a.flags = (reset ? 2 : 0) | ((flags & SCG_SC_SERIAL) ? 4 : 0);
+    const int obs_mode = !last_only ? 0 : final ? 1 : 2;
+    if (int rc = sc_launch_nodes_rollout(a, maxd, cfg->group, cfg->inbox_size, kc, obs_mode,
+                                         static_cast<hipStream_t>(stream)))
+      return rc;
+    const int64_t end = static_cast<int64_t>(st->time_step) + kc;  // <= T without auto-reset
+    if (reset) {
+      crossed += static_cast<int32_t>(end / T);
+      st->episode += static_cast<uint32_t>(end / T);
+      st->time_step = static_cast<int32_t>(end % T);
+    } else {
+      crossed += end == T ? 1 : 0;
+      st->time_step = static_cast<int32_t>(end);
+    }
+  }
+  if (n_done) *n_done = crossed;
   return SCG_OK;
 }
 

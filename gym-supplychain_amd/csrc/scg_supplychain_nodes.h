@@ -162,10 +162,13 @@ __host__ __device__ inline Num sc_nodes_act(const ScCtx& c, ScEnv& g, const Node
 // observation rows stored the same way: sc-2perstage 37.2-37.5 -> 35.7-37.0 us against
 // non-temporal stores, the two-product chain 86-88 -> 82-84 us (profiles/r06t_nodes_wt_ab*.log,
 // r06u_*, r06v_*).
+// copy_back = false (the rollout kernel's steps whose successor finds the state in LDS): the
+// entries, the size and nothing else stay in `lh` / `sz`; the env's state is not written.
 template <bool kStream = false, class Sink>
 __host__ __device__ inline void sc_nodes_heap(const ScCtx& c, ScEnv& g, const HeapView& lh, int32_t& sz,
                                               const NodesInbox& in, WordCache& ltc, const float* act, int t, int i,
-                                              int p, int& a_i, int& lt_i, Sink& out, bool receive = false) {
+                                              int p, int& a_i, int& lt_i, Sink& out, bool receive = false,
+                                              bool copy_back = true) {
   ScNode& nd = c.nodes[i];
   const int64_t q0 = nd.in_base + static_cast<int64_t>(p) * nd.in_deg;
   for (int k = 0; k < nd.in_deg; ++k) {  // in source order (:347)
@@ -193,6 +196,7 @@ __host__ __device__ inline void sc_nodes_heap(const ScCtx& c, ScEnv& g, const He
   SCG_ACCP(g.dbg, 2);
   const HeapView gh = sc_heap(c, g, i, p);
   sc_observe_bins(c, lh, sz, t, i, p, out, [&](int k, const HeapEntry& e) {  // copy back
+    if (!copy_back) return;
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (kStream) {
       __hip_atomic_store(&gh.tk[k * gh.stride], e.tk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -202,7 +206,7 @@ __host__ __device__ inline void sc_nodes_heap(const ScCtx& c, ScEnv& g, const He
 #endif
     gh.put(k, e);
   });
-  sc_size(c, g, i, p) = sz;
+  if (copy_back) sc_size(c, g, i, p) = sz;
   SCG_ACCP(g.dbg, 3);
 }
 
@@ -214,14 +218,14 @@ __host__ __device__ inline void sc_nodes_heap(const ScCtx& c, ScEnv& g, const He
 template <int MAXD, bool kKindPaths = false, class HeapAt, class Sink>
 __host__ __device__ inline double sc_nodes_serial(const ScCtx& c, ScEnv& g, const HeapAt& heap_at, int32_t* sz,
                                                   int64_t sz_stride, const NodesInbox& in, const float* act, int t,
-                                                  Sink& out) {
+                                                  Sink& out, bool copy_back = true) {
   Num total = pyint(0);
   for (int i = 0; i < c.n_nodes; ++i) {
     WordCache ltc{0, U4{0, 0, 0, 0}, false}, dmc{0, U4{0, 0, 0, 0}, false};
     int a_i = 0, lt_i = 0;
     for (int p = 0; p < c.P; ++p) {
       const int hp = i * c.P + p;
-      sc_nodes_heap(c, g, heap_at(hp), sz[hp * sz_stride], in, ltc, act, t, i, p, a_i, lt_i, out, true);
+      sc_nodes_heap(c, g, heap_at(hp), sz[hp * sz_stride], in, ltc, act, t, i, p, a_i, lt_i, out, true, copy_back);
     }
     if (!c.nodes[i].last_level) in.clear(c, i);
     sc_led_begin_node(c, g, i);

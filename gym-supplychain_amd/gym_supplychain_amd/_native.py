@@ -16,7 +16,7 @@ import torch  # noqa: F401  (loads the HIP runtime libscgpu.so binds to)
 
 LIB_NAME = "libscgpu.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 SCG_OK = 0
 SCG_ERR_INVALID = 1
@@ -32,6 +32,7 @@ SCG_DEMAND_UNIFORM = 3
 
 SCG_BG_AUTORESET = 1
 SCG_SC_SERIAL = 2  # node-parallel SupplyChain kernel: every env through its serial walk (tests)
+SCG_SC_LAST_OBS = 8  # scg_sc_rollout: obs is [N, n_obs], only the last step's observation is stored
 SCG_STREAM_DEMAND = 0
 SCG_STREAM_ACTION = 1
 SCG_STREAM_BG2_DEMAND = 4
@@ -172,6 +173,7 @@ SC_MAX_DESTS = 32
 SC_MAX_INIT = 16
 SC_MAX_NODES = 256
 SC_MAX_LEVELS = 16
+SC_ROLLOUT_MAX = 1024  # steps per fused rollout launch (the library loops beyond)
 SC_LEDGER_KEYS = 8  # info["sc_episode"] categories (supplychain_env.py:416-417)
 SC_LEDGER_NAMES = ("stock", "stock_pen", "supply", "process", "process_pen", "ship", "ship_pen", "unmet_dem")
 SC_KERNEL_AUTO, SC_KERNEL_LANE, SC_KERNEL_LEVEL, SC_KERNEL_STAGED, SC_KERNEL_NODES = 0, 1, 2, 3, 4
@@ -265,6 +267,10 @@ SIGNATURES = {
     "scg_sc_step": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _i32p,
                                    ctypes.c_void_p]),
+    "scg_sc_rollout": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_int32,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_uint32, _i32p, ctypes.c_void_p]),
+    "scg_sc_rollout_chunk": (ctypes.c_int, [ctypes.c_int32]),
     "scg_sc_draw_tables": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_uint32,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_nodes_max_blocks": (ctypes.c_int, [ctypes.c_int32]),

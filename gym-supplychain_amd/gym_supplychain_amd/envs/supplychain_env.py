@@ -214,6 +214,7 @@ class SupplyChainVecEnv:
 
     reset() -> obs [N, n_obs]
     step(actions float32 [N, n_actions] in [-1, 1]) -> (obs, reward float64 [N], done bool [N], info)
+    rollout(actions float32 [K, N, n_actions]) -> (obs [K, N, n_obs], rewards [K, N], dones [K]): K steps, one call
 
     Returned tensors are this env's output buffers (clone() to keep them). With
     auto_reset the terminal step resets every env in the same kernel; info then holds
@@ -441,6 +442,58 @@ class SupplyChainVecEnv:
         if self.build_info:
             return self._obs, self._rew, self._done_false, {"sc_episode": self._ledger_views(self._led, self._ret)}
         return self._obs, self._rew, self._done_false, {}
+
+    def rollout(self, actions, obs_out=None, rewards_out=None, last_obs_only=False):
+        """K steps in one call (scg_sc_rollout): the results of K step() calls, bit for bit.
+
+        actions float32 [K, N, n_actions] on the device. Returns (obs, rewards, dones): obs
+        [K, N, n_obs] in the env's obs dtype (with last_obs_only [N, n_obs], the last step's
+        observation alone), rewards float64 [K, N], dones a CPU bool tensor [K] (True where
+        step k was the episode's terminal one; the envs run in lock-step). With auto_reset a
+        rollout may cross any number of episode ends, and the obs row of a terminal step is
+        the reset observation, as in step(); without it a rollout past the terminal step
+        raises IndexError and leaves the env as it was. obs_out / rewards_out: buffers of
+        those shapes to fill instead of new ones.
+
+        On the node-parallel kernel without build_info the K steps run in one launch (per
+        1024 steps), each block keeping its envs' stocks and heaps in LDS from step to step;
+        every other kernel is stepped K times by the library. A rollout does not update the
+        buffers step() returns (its obs and reward views keep the last step() call's values);
+        terminal_observation, episode_return and final_return are updated as by step().
+        step() and rollout() may be mixed freely, and state_dict() after a rollout resumes
+        exactly.
+        """
+        a = actions
+        if not isinstance(a, torch.Tensor):
+            a = torch.as_tensor(np.asarray(a, dtype=np.float32))
+        if a.dtype != torch.float32 or a.device != self.device:
+            a = a.to(device=self.device, dtype=torch.float32)
+        if a.dim() != 3 or tuple(a.shape[1:]) != self._act_shape or a.shape[0] < 1:
+            raise ValueError(f"actions must be [K, {self.n_envs}, {self.n_actions}] with K >= 1, got {tuple(a.shape)}")
+        a = a.contiguous()
+        K = a.shape[0]
+        oshape = (self.n_envs, self.n_obs) if last_obs_only else (K, self.n_envs, self.n_obs)
+        if obs_out is None:
+            obs_out = torch.empty(oshape, dtype=self.obs_dtype, device=self.device)
+        elif (obs_out.dtype != self.obs_dtype or obs_out.device != self.device or tuple(obs_out.shape) != oshape or
+              not obs_out.is_contiguous()):
+            raise ValueError(f"obs_out must be a contiguous {self.obs_dtype} tensor {oshape} on {self.device}")
+        if rewards_out is None:
+            rewards_out = torch.empty((K, self.n_envs), dtype=torch.float64, device=self.device)
+        elif (rewards_out.dtype != torch.float64 or rewards_out.device != self.device or
+              tuple(rewards_out.shape) != (K, self.n_envs) or not rewards_out.is_contiguous()):
+            raise ValueError(f"rewards_out must be a contiguous float64 tensor {(K, self.n_envs)} on {self.device}")
+        t0, T = self._st.time_step, self.spec.total_time_steps
+        n_done = ctypes.c_int32(0)
+        flags = self._flags | (nat.SCG_SC_LAST_OBS if last_obs_only else 0)
+        nat.check(nat.lib.scg_sc_rollout(self._cfg_ref, self._st_ref, K, a.data_ptr(), obs_out.data_ptr(),
+                                         rewards_out.data_ptr(), self._term_ptr, flags, ctypes.byref(n_done),
+                                         self._stream()))
+        # step k runs time ((t0 + k) mod T) + 1 (without auto-reset t0 + K <= T)
+        dones = (torch.arange(t0 + 1, t0 + K + 1) % T) == 0
+        if n_done.value:
+            self.check_errors()
+        return obs_out, rewards_out, dones
 
     def _ledger_views(self, led, rewards):
         P, names = self.spec.P, nat.SC_LEDGER_NAMES

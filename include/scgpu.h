@@ -43,8 +43,10 @@ extern "C" {
  *   (scg_bg_server_slot, attach / detach / post / wait), mixing-hash check word; the
  *   SupplyChain step server (scg_sc_server_box, scg_sc_server, scg_sc_server_*).
  * 8: scg_bg_state ends with step_consts / step_consts_tag: the device block of the slab
- *   step kernel's launch constants (SCG_BG_STEP_CONSTS_BYTES). */
-#define SCG_ABI_VERSION 8
+ *   step kernel's launch constants (SCG_BG_STEP_CONSTS_BYTES).
+ * 9: scg_sc_rollout (K SupplyChain steps per call, SCG_SC_ROLLOUT_MAX, SCG_SC_LAST_OBS) and
+ *   the testing hook scg_sc_rollout_chunk. */
+#define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
 #define SCG_API __attribute__((visibility("default")))
@@ -78,6 +80,7 @@ typedef enum scg_demand_mode {
 #define SCG_BG_AUTORESET 1u /* at the terminal week reset in the same launch (VecEnv semantics) */
 #define SCG_SC_SERIAL 2u    /* node-parallel SupplyChain kernel: step every env with its serial
                                walk (the path of envs whose receive order it cannot prove; tests) */
+#define SCG_SC_LAST_OBS 8u  /* scg_sc_rollout: obs is [N][n_obs], only the last step's is stored */
 
 /* Philox streams (counter word 3) */
 #define SCG_STREAM_DEMAND 0u
@@ -391,7 +394,7 @@ SCG_API int scg_uniform_ints(uint64_t seed, int64_t env_offset, int64_t n_envs, 
  *
  *   SupplyChainEnv.__init__(nodes_info, ...)  :482-628  -> scg_sc_config + scg_sc_node[] + scg_sc_prepare
  *   SupplyChainEnv.reset()                    :630-682  -> scg_sc_reset
- *   SupplyChainEnv.step(action)               :703-748  -> scg_sc_step
+ *   SupplyChainEnv.step(action)               :703-748  -> scg_sc_step / scg_sc_rollout
  *     SC_Node.act :208-396, SC_Action.apply :42-98, heapq pipeline :398-400,
  *     _build_observation :762-791, SC_Node.build_observation :428-463 (all fused)
  * Per-episode randomness (customer demand table, stochastic lead times; the reference
@@ -405,6 +408,7 @@ SCG_API int scg_uniform_ints(uint64_t seed, int64_t env_offset, int64_t n_envs, 
 #define SCG_SC_MAX_NODES 256
 #define SCG_SC_MAX_LEVELS 16
 #define SCG_SC_LEDGER_KEYS 8 /* info['sc_episode'] cost/unit categories (:416-417) */
+#define SCG_SC_ROLLOUT_MAX 1024 /* steps per rollout launch; the host loops beyond */
 
 /* SupplyChain kernels (scg_sc_config.kernel) and the state layouts they use. */
 #define SCG_SC_KERNEL_AUTO 0
@@ -553,6 +557,31 @@ SCG_API int scg_sc_reset(const scg_sc_config* cfg, scg_sc_state* st, void* obs, 
 SCG_API int scg_sc_step(const scg_sc_config* cfg, scg_sc_state* st, const float* action, void* obs,
                         double* reward, void* terminal_obs, uint32_t flags, int32_t* done, void* stream);
 
+/* K steps in one call: the same results as n_steps calls of scg_sc_step with the same flags,
+ * bit for bit — every observation, reward, episode_return and final_return, the sticky
+ * error flag, the live heap entries in storage order, the heap sizes and the stocks
+ * afterwards, st->time_step and st->episode (heap slots past a heap's size may differ).
+ *   actions      DEVICE float32 [K][N][n_actions]
+ *   obs          DEVICE [K][N][n_obs] in the config's obs dtype; with SCG_SC_LAST_OBS
+ *                [N][n_obs], which receives only the last step's observation
+ *   rewards      DEVICE float64 [K][N]
+ *   terminal_obs optional [N][n_obs]: the observation of the last terminal step crossed
+ *   *n_done      the number of terminal steps crossed
+ *   flags        SCG_BG_AUTORESET | SCG_SC_SERIAL | SCG_SC_LAST_OBS
+ * With SCG_BG_AUTORESET a rollout may cross any number of episode ends (the obs row of a
+ * terminal step is then the reset observation, as in scg_sc_step); without it a rollout
+ * with time_step + n_steps > T fails with SCG_ERR_PAST_HORIZON. Every argument is checked
+ * before any HIP call, and a failed check leaves st untouched.
+ * Fused: a SCG_SC_KERNEL_NODES config on a state without ledgers runs in launches of up to
+ * SCG_SC_ROLLOUT_MAX steps, a block taking its 64 envs through all of a launch's steps with
+ * their stocks and heaps in LDS in between (HBM sees the state at the launch's last step and
+ * at auto-reset steps). Every other config (the lane, level and staged kernels, and the
+ * node-parallel one with build_info ledgers) is stepped by n_steps launches of scg_sc_step
+ * into the [k] slices: the same call and results, the per-step speed. */
+SCG_API int scg_sc_rollout(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const float* actions,
+                           void* obs, double* rewards, void* terminal_obs, uint32_t flags, int32_t* n_done,
+                           void* stream);
+
 /* The per-episode tables scg_sc_step draws (for tests): demand DEVICE int32
  * [N][T+1][R][P], leadtimes DEVICE int32 [N][T][n_leadtimes] (NULL when deterministic). */
 SCG_API int scg_sc_draw_tables(const scg_sc_config* cfg, const scg_sc_state* st, uint32_t episode,
@@ -631,6 +660,11 @@ SCG_API int scg_sc_server_stop(scg_sc_server* sv);
  * default: as many as the device holds at once), so a small batch runs several 64-env tiles
  * per block and the next-tile prefetch runs (scg_sc_nodes.hip). Returns the previous cap. */
 SCG_API int scg_sc_nodes_max_blocks(int32_t blocks);
+
+/* Testing hook: the fused scg_sc_rollout launches at most `steps` steps at a time (0, the
+ * default, and anything larger: SCG_SC_ROLLOUT_MAX), so a short rollout crosses launch
+ * boundaries. Returns the previous value. */
+SCG_API int scg_sc_rollout_chunk(int32_t steps);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """SupplyChain throughput (BASELINE configs 3 and 4) — one JSON line per scenario.
 
-    python tools/bench_sc.py [--scenario 2perstage|ntom|both] [--steps K] [--warmup W]
+    python tools/bench_sc.py [--scenario 2perstage|ntom|both] [--steps K] [--warmup W] [--rollout K]
 
 config 3: sc-2perstage-v0 defaults, 65,536 envs (8 nodes, 1 product, 14 actions, 27 obs)
 config 4: ntom = SupplyChainNPerStage([8, 8, 8, 16]) defaults (2 products), 262,144 envs
@@ -12,6 +12,10 @@ launch on the launch stream. `roofline.achieved` uses SURVEY §8(d)'s algorithmi
 env-step (2 x state + actions + observation + reward + demand: 1,148 B for config 3 and
 36,108 B for config 4). The CPU baseline times oracle.supplychain.SupplyChainOracle (the
 NumPy restatement of the reference step) on the host cores.
+--rollout K adds, in the same process after the per-step figure, SupplyChainVecEnv.rollout()
+of K steps per call (scg_sc_rollout, full [K, N, n_obs] observations), events around each
+call: the line's "rollout" entry holds the time per call and per step beside the per-step
+launches' median.
 """
 import argparse
 import json
@@ -90,7 +94,30 @@ def pmc_traffic(symbol, n_envs, name, kernel, build_info):
     return pmc_lookup("sc", workload, symbol.split("::")[-1])
 
 
-def run(name, steps, warmup, n_envs, cpu, kernel="auto", build_info=False):
+def time_rollout(env, k, calls, dev):
+    """`calls` rollouts of k steps each (after one warm-up call), events around each call."""
+    import statistics
+    import torch
+    gen = torch.Generator(device=dev).manual_seed(1)
+    acts = torch.rand((k, env.n_envs, env.n_actions), generator=gen, device=dev) * 2 - 1
+    obs = torch.empty((k, env.n_envs, env.n_obs), dtype=env.obs_dtype, device=dev)
+    rew = torch.empty((k, env.n_envs), dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    env.rollout(acts, obs_out=obs, rewards_out=rew)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
+    torch.cuda.synchronize()
+    for s, e in ev:
+        s.record(stream)
+        env.rollout(acts, obs_out=obs, rewards_out=rew)
+        e.record(stream)
+    torch.cuda.synchronize()
+    us = [s.elapsed_time(e) * 1e3 for s, e in ev]
+    return {"steps_per_call": k, "calls": calls, "us_per_call_median": statistics.median(us),
+            "us_per_step_median": statistics.median(us) / k, "us_per_step_min": min(us) / k,
+            "us_per_step_max": max(us) / k, "fused": env.kernel == "nodes" and not env.build_info}
+
+
+def run(name, steps, warmup, n_envs, cpu, kernel="auto", build_info=False, rollout=0, rollout_calls=10):
     import torch
     import gym_supplychain_amd as gsa
     sc = SCENARIOS[name]
@@ -116,6 +143,13 @@ def run(name, steps, warmup, n_envs, cpu, kernel="auto", build_info=False):
     if not os.environ.get("SCG_BENCH_NO_CHECK"):  # timing-only ablation builds break the dynamics
         env.check_errors()
     kern_s = sum(s.elapsed_time(e) for s, e in ev) / 1e3 / steps
+    rolled = None
+    if rollout:
+        import statistics
+        rolled = time_rollout(env, rollout, rollout_calls, dev)
+        rolled["step_launch_us_median"] = statistics.median(s.elapsed_time(e) * 1e3 for s, e in ev)
+        if not os.environ.get("SCG_BENCH_NO_CHECK"):
+            env.check_errors()
     bpe = sc["bytes_per_env_step"]
     achieved = bpe * N / kern_s / 1e9
     traffic, traffic_src = pmc_traffic(env.kernel_symbol, N, name, kernel, build_info)
@@ -131,6 +165,8 @@ def run(name, steps, warmup, n_envs, cpu, kernel="auto", build_info=False):
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "algorithmic_bytes_per_launch": bpe * N, "kernel": env.kernel_symbol,
                          "avg_kernel_us": kern_s * 1e6, "bytes_per_env_step": bpe}}
+    if rolled:
+        line["rollout"] = rolled
     del env, pool
     torch.cuda.empty_cache()
     if cpu:
@@ -147,6 +183,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel", default="auto", choices=["auto", "lane", "level", "staged", "nodes", "all", "both"])
     ap.add_argument("--build-info", action="store_true", help="keep the build_info ledgers (info['sc_episode'])")
+    ap.add_argument("--rollout", type=int, default=0, metavar="K",
+                    help="also time rollout() calls of K steps each (scg_sc_rollout)")
+    ap.add_argument("--rollout-calls", type=int, default=10)
     ap.add_argument("--nodes-max-blocks", type=int, default=0,
                     help="cap the node-parallel kernel's persistent grid (scg_sc_nodes_max_blocks; experiments)")
     a = ap.parse_args()
@@ -159,7 +198,8 @@ def main():
         if a.kernel in ("all", "both"):  # the node-parallel kernel only takes chains whose block fits LDS
             kernels = ["lane", "level", "staged"] + (["nodes"] if name != "ntom" else [])
         for k in kernels:
-            run(name, a.steps, a.warmup, a.envs, not a.no_cpu_baseline and k == kernels[-1], k, a.build_info)
+            run(name, a.steps, a.warmup, a.envs, not a.no_cpu_baseline and k == kernels[-1], k, a.build_info,
+                a.rollout, a.rollout_calls)
 
 
 if __name__ == "__main__":
