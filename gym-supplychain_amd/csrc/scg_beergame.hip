@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "scg_beergame_kernels.h"
+#include "scg_server_host.h"
 
 namespace scg {
 
@@ -504,26 +505,26 @@ struct ServerLock {
 
 static bool server_ok(const scg_bg_server* sv) { return sv && sv->box_host && sv->box_dev; }
 
+static const ServerNames kServerNames{"step server", "the wave's stream", "wave", "week"};
+
 // Launch the wave (lock held). It serves, first, every slot whose request is newer than its answer.
 static int server_launch_locked(scg_bg_server* sv) {
-  const uint32_t exit_seen = __atomic_load_n(&sv->box_host->exit_req, __ATOMIC_ACQUIRE);
-  const uint32_t idle_ticks = static_cast<uint32_t>(sv->idle_us) * 100u;  // 100 MHz real-time clock
-  if (int rc = launch_server(sv->levels, sv->demand_mode, static_cast<hipStream_t>(sv->stream), sv->box_dev,
-                             exit_seen, idle_ticks))
-    return rc;
-  sv->running = 1;
-  sv->launches += 1;
-  sv->last_ns = mono_ns();
-  return SCG_OK;
+  return server_launch(sv, [sv](uint32_t exit_seen, uint32_t idle_ticks) {
+    return launch_server(sv->levels, sv->demand_mode, static_cast<hipStream_t>(sv->stream), sv->box_dev, exit_seen,
+                         idle_ticks);
+  });
 }
 
 static int server_stop_locked(scg_bg_server* sv) {
-  if (!sv->running) return SCG_OK;
-  __atomic_store_n(&sv->box_host->exit_req, sv->box_host->exit_req + 1, __ATOMIC_RELEASE);
-  sv->running = 0;
-  if (hipStreamSynchronize(static_cast<hipStream_t>(sv->stream)) != hipSuccess)
-    return fail(SCG_ERR_HIP, "step server: hipStreamSynchronize failed");
-  return SCG_OK;
+  return server_retire(sv, [sv] { return stream_wait(sv->stream); }, kServerNames.who);
+}
+
+// The wave polls slots 0 .. n_slots - 1: up to the highest attached one (lock held).
+static void server_publish_n_slots(scg_bg_server* sv) {
+  uint32_t ns = 0;
+  for (int j = 0; j < kServerSlots; ++j)
+    if (sv->slots_used >> j & 1u) ns = j + 1;
+  __atomic_store_n(&sv->box_host->n_slots, ns, __ATOMIC_RELEASE);
 }
 
 int scg_bg_server_stop(scg_bg_server* sv) {
@@ -563,10 +564,7 @@ int scg_bg_server_attach(scg_bg_server* sv, scg_bg_server_slot* slot) {
   slot->done = 0;
   slot->relaunches = 0;
   __atomic_store_n(&b->done_seq[k], slot->seq, __ATOMIC_RELEASE);
-  uint32_t ns = 0;
-  for (int j = 0; j < kServerSlots; ++j)
-    if (sv->slots_used >> j & 1u) ns = j + 1;
-  __atomic_store_n(&b->n_slots, ns, __ATOMIC_RELEASE);
+  server_publish_n_slots(sv);
   return SCG_OK;
 }
 
@@ -580,10 +578,7 @@ int scg_bg_server_detach(scg_bg_server_slot* slot) {
     return fail(SCG_ERR_INVALID, "step server: detach with a request of slot %d unanswered", k);
   ServerLock lk(sv);
   sv->slots_used &= ~(1u << k);
-  uint32_t ns = 0;
-  for (int j = 0; j < kServerSlots; ++j)
-    if (sv->slots_used >> j & 1u) ns = j + 1;
-  __atomic_store_n(&b->n_slots, ns, __ATOMIC_RELEASE);
+  server_publish_n_slots(sv);
   slot->index = -1;
   return SCG_OK;
 }
@@ -619,7 +614,7 @@ int scg_bg_server_post(const scg_bg_config* cfg, scg_bg_state* st, scg_bg_server
     slot->gen = slot->gen + 1 ? slot->gen + 1 : 1;  // 0 is the wave's "none loaded"
   }
   // a wave idle for more than half its time-out may be exiting: retire it before posting
-  if (sv->running && mono_ns() - sv->last_ns > static_cast<int64_t>(sv->idle_us) * 500)
+  if (server_stale(sv, mono_ns()))
     if (int rc = server_stop_locked(sv)) return rc;
   uint32_t line[16] = {0};
   const uint32_t seq = slot->seq + 1;
@@ -632,9 +627,7 @@ int scg_bg_server_post(const scg_bg_config* cfg, scg_bg_state* st, scg_bg_server
   line[6] = slot->gen;
   for (int l = 0; l < n_inline; ++l) line[8 + l] = static_cast<uint32_t>(slot->action_host[l]);
   line[7] = server_line_check(line);
-  uint32_t* dst = reinterpret_cast<uint32_t*>(&b->req[k]);
-  for (int i = 1; i < 16; ++i) __atomic_store_n(&dst[i], line[i], __ATOMIC_RELAXED);
-  __atomic_store_n(&dst[0], seq, __ATOMIC_RELEASE);
+  server_publish(reinterpret_cast<uint32_t*>(&b->req[k]), line);
   slot->seq = seq;
   slot->week = w;
   slot->done = (wk.flags & 1) ? 1 : 0;
@@ -648,39 +641,11 @@ int scg_bg_server_wait(scg_bg_state* st, scg_bg_server_slot* slot, int64_t spin_
   if (!st || !slot || !server_ok(slot->server) || slot->index < 0 || slot->index >= kServerSlots)
     return fail(SCG_ERR_INVALID, "step server: the slot is not attached");
   scg_bg_server* sv = slot->server;
-  scg_bg_server_box* b = sv->box_host;
-  const int k = slot->index;
-  const uint32_t seq = slot->seq;
-  const int64_t start = mono_ns();
-  const int64_t check_ns = (sv->check_us > 0 ? sv->check_us : 2000000) * int64_t(1000);
-  int64_t check = start + check_ns;
-  int gone = 0;
-  for (uint32_t spins = 0;; ++spins) {
-    if (__atomic_load_n(&b->done_seq[k], __ATOMIC_ACQUIRE) == seq) break;
-    cpu_relax();
-    if ((spins & 255u) != 255u) continue;
-    const int64_t now = mono_ns();
-    if (spin_us >= 0 && now - start > spin_us * 1000) return SCG_PENDING;
-    if (now < check) continue;
-    check = now + check_ns;
-    // Every check interval: a wave that has exited without serving the request (its stream
-    // idle: a host stall past its time-out, an exit another thread asked for) is launched
-    // again — it serves pending requests first — once per wait; a HIP error on the stream
-    // fails at once; a wave still queued or running is waited for, up to 60 s in all.
-    ServerLock lk(sv);
-    const hipError_t q = hipStreamQuery(static_cast<hipStream_t>(sv->stream));
-    if (q != hipSuccess && q != hipErrorNotReady)
-      return fail(SCG_ERR_HIP, "step server: the wave's stream reports %s (week %d)", hipGetErrorString(q), slot->week);
-    if (__atomic_load_n(&b->done_seq[k], __ATOMIC_ACQUIRE) == seq) break;
-    if (q == hipSuccess) {
-      if (gone++ > 0) return fail(SCG_ERR_HIP, "step server: the wave exits without answering (week %d)", slot->week);
-      sv->running = 0;
-      slot->relaunches += 1;
-      if (int rc = server_launch_locked(sv)) return rc;
-    }
-    if (now - start > 60000000000LL) return fail(SCG_ERR_HIP, "step server: no answer for 60 s (week %d)", slot->week);
-  }
-  sv->last_ns = mono_ns();
+  if (int rc = server_await<ServerLock>(
+          sv, &sv->box_host->done_seq[slot->index], slot->seq, spin_us, &slot->relaunches,
+          [sv](const char** text) { return stream_state(sv->stream, text); },
+          [sv] { return server_launch_locked(sv); }, kServerNames, slot->week))
+    return rc;  // SCG_PENDING or an error
   st->week = slot->week;  // no auto-reset on this path
   if (done) *done = slot->done;
   return SCG_OK;

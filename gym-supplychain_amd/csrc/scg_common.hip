@@ -28,6 +28,16 @@ int check_launch(const char* what) {
   return SCG_OK;
 }
 
+StreamState stream_state(void* stream, const char** text) {
+  const hipError_t q = hipStreamQuery(static_cast<hipStream_t>(stream));
+  if (q == hipSuccess) return kStreamIdle;
+  if (q == hipErrorNotReady) return kStreamBusy;
+  *text = hipGetErrorString(q);
+  return kStreamError;
+}
+
+bool stream_wait(void* stream) { return hipStreamSynchronize(static_cast<hipStream_t>(stream)) == hipSuccess; }
+
 const char* last_error() { return g_err; }
 
 // STREAM copy for the measured HBM peak (bench.py roofline.measured_peak). The copy shapes

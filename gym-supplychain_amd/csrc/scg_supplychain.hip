@@ -17,6 +17,7 @@
 
 #include "scg_common.h"
 #include "scg_mailbox.h"
+#include "scg_server_host.h"
 
 // Diagnostic build only (-DSCG_SC_STAMPS, tools/sc_stamps.py): lane 0 of every wave of the
 // LDS lane kernel records the shader clock at phase boundaries into a buffer of its own
@@ -931,13 +932,10 @@ static_assert(sizeof(scg_sc_server_box) == 192 && offsetof(scg_sc_server_box, ac
                   offsetof(scg_sc_server_box, done_seq) == 128,
               "SupplyChain mailbox");
 static_assert(sizeof(scg_sc_server) == 104, "SupplyChain server struct");
+static const ServerNames kScServerNames{"SupplyChain step server", "the stream", "block", "step"};
+
 static int sc_server_stop_now(scg_sc_server* sv) {
-  if (!sv->running) return SCG_OK;
-  __atomic_store_n(&sv->box_host->exit_req, sv->box_host->exit_req + 1, __ATOMIC_RELEASE);
-  sv->running = 0;
-  if (hipStreamSynchronize(static_cast<hipStream_t>(sv->stream)) != hipSuccess)
-    return fail(SCG_ERR_HIP, "SupplyChain step server: hipStreamSynchronize failed");
-  return SCG_OK;
+  return server_retire(sv, [sv] { return stream_wait(sv->stream); }, kScServerNames.who);
 }
 
 int scg_sc_server_stop(scg_sc_server* sv) {
@@ -951,15 +949,10 @@ static int sc_server_launch(const scg_sc_config* cfg, const scg_sc_state* st, sc
   a.obs = sv->obs;
   a.rew = sv->reward;
   a.term_obs = nullptr;
-  const uint32_t exit_seen = __atomic_load_n(&sv->box_host->exit_req, __ATOMIC_ACQUIRE);
-  if (int rc = sc_launch_nodes_server(a, sc_maxd_bucket(cfg->max_dests), cfg->group, cfg->inbox_size,
-                                      static_cast<hipStream_t>(sv->stream), sv->box_dev, exit_seen,
-                                      static_cast<uint32_t>(sv->idle_us) * 100u))
-    return rc;
-  sv->running = 1;
-  sv->launches += 1;
-  sv->last_ns = mono_ns();
-  return SCG_OK;
+  return server_launch(sv, [&](uint32_t exit_seen, uint32_t idle_ticks) {
+    return sc_launch_nodes_server(a, sc_maxd_bucket(cfg->max_dests), cfg->group, cfg->inbox_size,
+                                  static_cast<hipStream_t>(sv->stream), sv->box_dev, exit_seen, idle_ticks);
+  });
 }
 
 int scg_sc_server_post(const scg_sc_config* cfg, scg_sc_state* st, scg_sc_server* sv) {
@@ -980,7 +973,7 @@ int scg_sc_server_post(const scg_sc_config* cfg, scg_sc_state* st, scg_sc_server
     return fail(SCG_ERR_INVALID, "SupplyChain step server: a post while the last request is unanswered");
   const int t = st->time_step + 1;
   // a block idle for more than half its time-out may be exiting: retire it before posting
-  if (sv->running && mono_ns() - sv->last_ns > static_cast<int64_t>(sv->idle_us) * 500)
+  if (server_stale(sv, mono_ns()))
     if (int rc = sc_server_stop_now(sv)) return rc;
   // the request line and the inline action row: one env of at most 16 actions travels in
   // the request, so the block does not read it across PCIe
@@ -995,9 +988,7 @@ int scg_sc_server_post(const scg_sc_config* cfg, scg_sc_state* st, scg_sc_server
   if (inline_act) std::memcpy(&line[16], sv->action_host, sizeof(float) * cfg->n_actions);
   line[7] = mailbox_check(line);
   sv->reload = 0;
-  uint32_t* dst = reinterpret_cast<uint32_t*>(b);
-  for (int i = 1; i < 32; ++i) __atomic_store_n(&dst[i], line[i], __ATOMIC_RELAXED);
-  __atomic_store_n(&dst[0], seq, __ATOMIC_RELEASE);
+  server_publish(reinterpret_cast<uint32_t*>(b), line);
   sv->seq = seq;
   sv->t = t;
   sv->done = t == T ? 1 : 0;
@@ -1010,36 +1001,11 @@ int scg_sc_server_post(const scg_sc_config* cfg, scg_sc_state* st, scg_sc_server
 int scg_sc_server_wait(const scg_sc_config* cfg, scg_sc_state* st, scg_sc_server* sv, int64_t spin_us, int32_t* done) {
   if (int rc = sc_check(cfg, st)) return rc;
   if (!sv || !sv->box_host) return fail(SCG_ERR_INVALID, "null server/mailbox");
-  scg_sc_server_box* b = sv->box_host;
-  const uint32_t seq = sv->seq;
-  const int64_t start = mono_ns();
-  const int64_t check_ns = (sv->check_us > 0 ? sv->check_us : 2000000) * int64_t(1000);
-  int64_t check = start + check_ns;
-  int gone = 0;
-  for (uint32_t spins = 0;; ++spins) {
-    if (__atomic_load_n(&b->done_seq, __ATOMIC_ACQUIRE) == seq) break;
-    cpu_relax();
-    if ((spins & 255u) != 255u) continue;
-    const int64_t now = mono_ns();
-    if (spin_us >= 0 && now - start > spin_us * 1000) return SCG_PENDING;
-    if (now < check) continue;
-    check = now + check_ns;
-    // the BeerGame server's checks (scg_bg_server_wait): a HIP error at once; a block gone
-    // without answering launched again once (it serves the pending request first)
-    const hipError_t q = hipStreamQuery(static_cast<hipStream_t>(sv->stream));
-    if (q != hipSuccess && q != hipErrorNotReady)
-      return fail(SCG_ERR_HIP, "SupplyChain step server: the stream reports %s (step %d)", hipGetErrorString(q), sv->t);
-    if (__atomic_load_n(&b->done_seq, __ATOMIC_ACQUIRE) == seq) break;
-    if (q == hipSuccess) {
-      if (gone++ > 0)
-        return fail(SCG_ERR_HIP, "SupplyChain step server: the block exits without answering (step %d)", sv->t);
-      sv->running = 0;
-      sv->relaunches += 1;
-      if (int rc = sc_server_launch(cfg, st, sv)) return rc;
-    }
-    if (now - start > 60000000000LL) return fail(SCG_ERR_HIP, "SupplyChain step server: no answer for 60 s (step %d)", sv->t);
-  }
-  sv->last_ns = mono_ns();
+  if (int rc = server_await<NoLock>(
+          sv, &sv->box_host->done_seq, sv->seq, spin_us, &sv->relaunches,
+          [sv](const char** text) { return stream_state(sv->stream, text); },
+          [=] { return sc_server_launch(cfg, st, sv); }, kScServerNames, sv->t))
+    return rc;  // SCG_PENDING or an error
   st->time_step = sv->t;  // no auto-reset on this path
   if (done) *done = sv->done;
   return SCG_OK;

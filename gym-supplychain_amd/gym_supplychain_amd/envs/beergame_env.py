@@ -12,10 +12,10 @@ Differences from the reference, all documented in DESIGN.md:
   * BeerGameVecEnv adds per-env demand (a device table, or Poisson draws made on device
     with Philox4x32-10) and auto-reset; the reference has one fixed demand list (F2).
 """
-import atexit
 import ctypes
 import numbers
 import os
+import threading
 import weakref
 
 import numpy as np
@@ -25,6 +25,7 @@ from .. import _native as nat
 from .. import checkpoint as ckpt
 from .. import spaces
 from . import resident
+from .step_server import _ResidentServer
 from ..distributed import entropy_seed
 
 # beergame_env.py:16-23
@@ -537,67 +538,42 @@ class BeerGameVecEnv:
         pass
 
 
-_SERVERS = {}  # (device index, levels, demand mode) -> _StepServer, one resident wave each
+# (device index, levels, demand mode, j) -> _StepServer: server j of that kind, one resident wave each
+_SERVERS = {}
+_ATTACH_LOCK = threading.Lock()  # envs may be constructed from several threads
 
 
-@atexit.register
-def _stop_servers():  # no step-server wave outlives the interpreter (nor its mailbox)
-    for sv in list(_SERVERS.values()):
-        sv.close()
-
-
-class _StepServer:
-    """A step server (include/scgpu.h scg_bg_server_*): one wave on a non-blocking,
-    high-priority stream of its own polls a mailbox in host-mapped memory and runs each week
-    an attached env posts on that env's state. One per (device, levels, demand mode) in a
-    process, whatever the number of drop-in envs (up to BG_SERVER_SLOTS per server; more
-    start another server): many envs stepped in turn share one resident wave and one stream.
-    The high priority puts the stream on a hardware queue of its own pool, so the parked wave
-    never holds up work of normal-priority streams that would share its queue; and at most one
-    server per device is resident at a time (envs/resident.py). The wave exits
-    when stopped, or by itself after IDLE_US without a request; a post launches it again when
-    needed. The mailbox is freed only after the wave has been stopped."""
-
-    IDLE_US = 20000
+class _StepServer(_ResidentServer):
+    """A step server (include/scgpu.h scg_bg_server_*): one wave on a stream of its own
+    (envs/step_server.py) polls a mailbox in host-mapped memory and runs each week an attached
+    env posts on that env's state. One per (device, levels, demand mode) in a process, whatever
+    the number of drop-in envs (up to BG_SERVER_SLOTS per server; more start another server):
+    many envs stepped in turn share one resident wave and one stream. The high priority puts
+    the stream on a hardware queue of its own pool, so the parked wave never holds up work of
+    normal-priority streams that would share its queue; and at most one server per device is
+    resident at a time (envs/resident.py)."""
 
     @classmethod
     def attach(cls, vec, act_dev, act_host, obs_dev, rew_dev):
         """A slot of this process's server for `vec` (a free one, or a new server)."""
         key0 = (vec._dev_index, int(vec._cfg.levels), int(vec._cfg.demand_mode))
-        for j in range(64):
-            key = key0 + (j,)
-            sv = _SERVERS.get(key)
-            if sv is None:
-                sv = _SERVERS[key] = cls(vec.device, key0[1], key0[2], key)
-            if bin(sv.sv.slots_used).count("1") < nat.BG_SERVER_SLOTS:
-                return _ServerSlot(sv, vec, act_dev, act_host, obs_dev, rew_dev)
+        with _ATTACH_LOCK:  # the free-slot count and the attach are one step
+            for j in range(64):
+                key = key0 + (j,)
+                sv = _SERVERS.get(key)
+                if sv is None:
+                    sv = _SERVERS[key] = cls(vec.device, key0[1], key0[2], key)
+                if bin(sv.sv.slots_used).count("1") < nat.BG_SERVER_SLOTS:
+                    return _ServerSlot(sv, vec, act_dev, act_host, obs_dev, rew_dev)
         raise RuntimeError("too many drop-in envs on one device for the step server")
 
     def __init__(self, device, levels, demand_mode, key):
-        stream, self.priority = resident.server_stream(device)
-        self._device, self._dev_index, self._key = device, key[0], key
-        self._box = box = nat.MappedBuffer(ctypes.sizeof(nat.BgServerBox))
-        self.box = nat.BgServerBox.from_address(box.host)
-        self.sv = nat.BgServer(box.host, box.dev, stream, levels, demand_mode, self.IDLE_US, 0)
-        self._closed = False
-
-    @property
-    def launches(self):
-        return int(self.sv.launches)
-
-    def stop(self):
-        if not self._closed:
-            with torch.cuda.device(self._device):
-                nat.check(nat.lib.scg_bg_server_stop(ctypes.byref(self.sv)))
+        super().__init__(device, key[0], nat.BgServerBox, nat.lib.scg_bg_server_stop)
+        self._key = key
+        self.sv = nat.BgServer(*self.box_addrs, self.stream, levels, demand_mode, self.IDLE_US, 0)
 
     def close(self):
-        if self._closed:
-            return
-        self.stop()  # raises if the wave cannot be stopped: then the mailbox stays allocated
-        self._closed = True
-        resident.release(self._dev_index, self)
-        resident.destroy_stream(self.sv.stream)
-        self._box = None
+        super().close()
         if _SERVERS.get(self._key) is self:
             del _SERVERS[self._key]
 
@@ -801,13 +777,18 @@ class BeerGameEnv(spaces.Env):
         print('Backlog costs:\t', self.backlog_costs)
 
     def close(self):
-        if self._server is not None:
-            self._server.close()
-
-    def __del__(self):
+        """Give the slot back. The reference's close() does nothing and stepping may go on: a
+        later step() launches the step kernel (the wave wrote every week's state to memory)."""
         server = getattr(self, "_server", None)
         if server is not None:
             server.close()
+            self._server = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter teardown
+            pass
 
     def _observation(self):
         return self.inventory - self.backlog

@@ -9,6 +9,11 @@ parked wave would wait for its time-out. So before a server posts, `claim` stops
 other server of the device may be resident. The BeerGame server serves every drop-in
 BeerGameEnv of a level count from one wave, so envs of one kind stepped in turn never
 switch; only stepping different kinds in turn costs a stop and a launch per switch.
+
+Restriction: servers of different kinds must not be stepped from concurrent threads. A
+`claim` from one thread may stop a server between another thread's post and its wait; that
+wait stalls for a check interval (2 s) and then launches its server again without claiming
+the device (csrc/scg_server_host.h).
 """
 import ctypes
 import threading

@@ -19,11 +19,9 @@ Differences from the reference:
   * build_info=True keeps info['sc_episode'] on the device (lane and staged kernels); the
     drop-in env returns it with the reference's per-entry NumPy types.
 """
-import atexit
 import ctypes
 import hashlib
 import os
-import weakref
 
 import numpy as np
 import torch
@@ -33,6 +31,7 @@ from .. import checkpoint as ckpt
 from .. import spaces
 from . import demand
 from . import resident
+from .step_server import _ResidentServer
 from ..distributed import entropy_seed
 
 _MAXP = nat.SC_MAX_PRODUCTS
@@ -589,7 +588,9 @@ class SupplyChainVecEnv:
 
     def load_state_dict(self, state):
         """Restore a state_dict() of an env of the same chain and batch (ValueError
-        otherwise); the copies are enqueued on the current stream."""
+        otherwise); the copies are enqueued on the current stream. On the vec env inside a
+        drop-in SupplyChainEnv (which has no load_state_dict of its own) this is an out-of-band
+        state write: stop the env's step server or set its sv.reload first (_ScStepServer)."""
         bufs = self._ckpt_buffers()
         ckpt.check(state, type(self).__name__, self._ckpt_fingerprint(), bufs)
         cnt = ckpt.restore(state, bufs)
@@ -695,66 +696,26 @@ class SC_NodeView:
         return f"{self.label} ({self.shipments_by_prod}) [{np.round(self.stock, 1)}]"
 
 
-class _ScStepServer:
+class _ScStepServer(_ResidentServer):
     """The drop-in SupplyChainEnv's step server (include/scgpu.h scg_sc_server_*): one
-    resident block of the node-parallel kernel's shape on a non-blocking, high-priority stream
-    of its own polls a host-mapped mailbox and runs each posted step on the env's state (the
-    batch kernel's tile code), writing observation and reward to the env's host-mapped block.
-    It exits when stopped (reset(), close(), another server of the device becoming resident,
-    interpreter exit) or by itself after IDLE_US without a request; step() launches it again
-    when needed. The mailbox is freed only after the block has been stopped."""
-
-    IDLE_US = 20000
+    resident block of the node-parallel kernel's shape on a stream of its own
+    (envs/step_server.py) polls a host-mapped mailbox and runs each posted step on the env's
+    state (the batch kernel's tile code), writing observation and reward to the env's
+    host-mapped block. reset() does not stop the block: between two steps it keeps the state in
+    its LDS only while the request continues the same episode at t == last t + 1 (the
+    keep-state rule), and reads it from memory otherwise, as after a reset. Anything else that
+    writes the state out of band (the vec env's load_state_dict() with a matching time step)
+    must set sv.reload or stop() the server first."""
 
     def __init__(self, vec, act_dev, act_host, obs_dev, rew_dev):
-        stream, self.priority = resident.server_stream(vec.device)
-        self._dev_index = vec._dev_index
-        self._device = vec.device
-        self._box = box = nat.MappedBuffer(ctypes.sizeof(nat.ScServerBox))
-        self.box = nat.ScServerBox.from_address(box.host)
-        self.sv = nat.ScServer(box.host, box.dev, stream, act_dev, act_host, obs_dev, rew_dev, self.IDLE_US, 0)
+        super().__init__(vec.device, vec._dev_index, nat.ScServerBox, nat.lib.scg_sc_server_stop)
+        self.sv = nat.ScServer(*self.box_addrs, self.stream, act_dev, act_host, obs_dev, rew_dev, self.IDLE_US, 0)
         self._args = (vec._cfg_addr, vec._st_addr, ctypes.addressof(self.sv))
         self._fast = nat.fast.sc_server_step
-        self._closed = False
-        _SC_SERVERS.add(self)
-
-    @property
-    def launches(self):
-        return int(self.sv.launches)
 
     def step(self):
         resident.claim(self._dev_index, self)
         return self._fast(*self._args)
-
-    def stop(self):
-        if not self._closed:
-            with torch.cuda.device(self._device):
-                nat.check(nat.lib.scg_sc_server_stop(ctypes.byref(self.sv)))
-
-    def close(self):
-        if self._closed:
-            return
-        self.stop()  # raises if the block cannot be stopped: then the mailbox stays allocated
-        self._closed = True
-        resident.release(self._dev_index, self)
-        resident.destroy_stream(self.sv.stream)
-        self._box = None
-        _SC_SERVERS.discard(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter teardown
-            pass
-
-
-_SC_SERVERS = weakref.WeakSet()
-
-
-@atexit.register
-def _stop_sc_servers():  # no server block outlives the interpreter (nor its mailbox)
-    for sv in list(_SC_SERVERS):
-        sv.close()
 
 
 class SupplyChainEnv(spaces.Env):
@@ -959,9 +920,12 @@ class SupplyChainEnv(spaces.Env):
         print('Current reward:', round(float(self.current_reward), 3))
 
     def close(self):
+        """Stop and free the step server. The reference's close() does nothing and stepping may
+        go on: a later step() launches the kernel (the block wrote every step's state to memory)."""
         server = getattr(self, "_server", None)
         if server is not None:
             server.close()
+            self._server = None
 
     def __del__(self):
         try:

@@ -149,6 +149,36 @@ def test_sc_block_gone_without_answering_is_relaunched(monkeypatch):
     ref.close()
 
 
+def test_sc_close_mid_episode_then_stepping_goes_on(monkeypatch):
+    """close() stops the block, frees its mailbox and stream and drops the server; the
+    reference's close() does nothing, so the episode goes on: the remaining steps, a reset()
+    and a whole further episode run on the launch path from the state the block wrote, equal
+    to the launch-path twin throughout."""
+    T = 12
+    srv, ref = _pair(monkeypatch, T=T, seed=13)
+    rng = np.random.RandomState(13)
+
+    def act():
+        return rng.uniform(-1, 1, srv.action_space.shape).astype(np.float32)
+
+    assert np.array_equal(srv.reset(), ref.reset())
+    for t in range(5):
+        _same(srv, ref, act(), ("server", t))
+    srv.close()
+    assert srv._server is None
+    for t in range(5, T):
+        done = _same(srv, ref, act(), ("after close", t))
+    assert done
+    assert np.array_equal(srv.stock, ref.stock) and repr(srv.shipments()) == repr(ref.shipments())
+    assert np.array_equal(srv.reset(), ref.reset())
+    for t in range(T):
+        done = _same(srv, ref, act(), ("second episode", t))
+    assert done
+    assert np.array_equal(srv.stock, ref.stock) and repr(srv.shipments()) == repr(ref.shipments())
+    srv.close()
+    ref.close()
+
+
 def test_sc_device_synchronize_after_a_step_is_bounded(monkeypatch):
     """torch.cuda.synchronize() right after a step waits for the parked block's time-out
     (20 ms): within 25 ms."""

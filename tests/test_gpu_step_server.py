@@ -265,6 +265,73 @@ def test_dropin_envs_stepped_from_threads(monkeypatch):
         envs[k].close()
 
 
+def test_close_mid_episode_then_stepping_goes_on(monkeypatch):
+    """close() gives the slot back and drops it; the reference's close() does nothing, so the
+    episode goes on: the remaining weeks, a reset() and a whole further episode run on the
+    launch path from the state the wave wrote, equal to the launch-path twin throughout."""
+    T, L = 12, 4
+    srv, ref = _pair(_info(L, T, 31), monkeypatch)
+    rng = np.random.RandomState(31)
+    assert np.array_equal(srv.reset(), ref.reset())
+    for w in range(5):
+        _same(srv, ref, rng.randint(-3, 15, L), ("server", w))
+    srv.close()
+    assert srv._server is None
+    for w in range(5, T):
+        _same(srv, ref, rng.randint(-3, 15, L), ("after close", w))
+    _same_state(srv, ref, "after close")
+    assert np.array_equal(srv.reset(), ref.reset())
+    for w in range(T):
+        _same(srv, ref, rng.randint(-3, 15, L), ("second episode", w))
+    _same_state(srv, ref, "second episode")
+    srv.close()
+    ref.close()
+
+
+def test_envs_constructed_from_threads_fill_two_servers(monkeypatch):
+    """BG_SERVER_SLOTS + 2 drop-in envs constructed from 4 threads at once: picking a server
+    and attaching to it is one step, so every constructor succeeds, the envs fill exactly two
+    servers with distinct slots in each, and each env steps as its launch-path twin does."""
+    from gym_supplychain_amd import BeerGameEnv
+    from gym_supplychain_amd import _native as nat
+    T, L = 12, 4
+    n = nat.BG_SERVER_SLOTS + 2
+    infos = [_info(L, T, 400 + k) for k in range(n)]
+    monkeypatch.setenv("SCG_BG_SERVER", "1")
+    envs = [None] * n
+    errors = []
+    go = threading.Barrier(4)
+
+    def construct(ks):
+        try:
+            go.wait(30)
+            for k in ks:
+                envs[k] = BeerGameEnv(infos[k])
+        except Exception as exc:  # pragma: no cover - reported below
+            errors.append(exc)
+
+    threads = [threading.Thread(target=construct, args=(range(j, n, 4),)) for j in range(4)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(60)
+    assert not errors, errors
+    by_server = {}
+    for e in envs:
+        by_server.setdefault(id(e._server.server), []).append(e._server.slot.index)
+    assert len(by_server) == 2 and sorted(len(v) for v in by_server.values()) == [2, nat.BG_SERVER_SLOTS]
+    assert all(len(set(v)) == len(v) for v in by_server.values())
+    monkeypatch.setenv("SCG_BG_SERVER", "0")
+    rng = np.random.RandomState(6)
+    for k, e in enumerate(envs):
+        ref = BeerGameEnv(infos[k])
+        assert ref._server is None
+        assert np.array_equal(e.reset(), ref.reset())
+        _same(e, ref, rng.randint(0, 15, L), k)
+        e.close()
+        ref.close()
+
+
 def test_server_slot_with_several_envs_through_the_c_abi():
     """A slot serves up to 64 envs (include/scgpu.h scg_bg_server_*): a 5-env BeerGameVecEnv
     (separate state buffers) stepped through scg_bg_server_step, its action row read from
