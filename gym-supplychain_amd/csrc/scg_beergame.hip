@@ -377,7 +377,7 @@ int scg_bg_prepare(scg_bg_config* cfg) {
       mode = MODE_STORE;
       written[w + d] = 1;
     }
-    cfg->plan[w] = mode | (written[w] ? PLAN_ARRIVE : 0) | (d << 8);
+    cfg->plan[w] = mode | (written[w] ? PLAN_ARRIVE : 0) | (d << kPlanDelayShift);
   }
   cfg->ring_slots = R;
   return SCG_OK;

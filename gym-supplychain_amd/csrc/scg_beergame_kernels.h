@@ -42,7 +42,10 @@ enum : int32_t { MODE_DIRECT = 0, MODE_STORE = 1, MODE_ADD = 2, MODE_DROP = 3 };
 constexpr int32_t PLAN_ARRIVE = 4;
 inline int32_t plan_mode(int32_t p) { return p & 3; }
 inline bool plan_arrive(int32_t p) { return (p & PLAN_ARRIVE) != 0; }
-inline int32_t plan_delay(int32_t p) { return (p >> 8) & 0xff; }
+// bits 8 and up hold the week's whole delay (the word is non-negative)
+constexpr int kPlanDelayShift = 8;
+static_assert(static_cast<int64_t>(SCG_BG_MAX_DELAY) << kPlanDelayShift <= INT32_MAX, "plan delay field too narrow");
+inline int32_t plan_delay(int32_t p) { return p >> kPlanDelayShift; }
 
 constexpr int kBlock = 256;
 

@@ -87,11 +87,30 @@ def _expected_plan(delays, T):
     return plan
 
 
-@pytest.mark.parametrize("seed", range(8))
+LONG_DELAY_HORIZONS = (300, 520, 1000, 4096)
+
+
+def _long_delays(rng, T):
+    """Delays 0..3 with 255, 256, 257 and 4096 (SCG_BG_MAX_DELAY) among the first 40 weeks: 256
+    and 255 in consecutive weeks (one arrival week, stored then accumulated), the rest at
+    random weeks; whether each arrives inside the horizon depends on T."""
+    delays = rng.randint(0, 4, size=T)
+    w = int(rng.randint(1, 20))
+    delays[w - 1], delays[w] = 256, 255
+    for d, k in zip((255, 256, 257, 4096, 4096), rng.choice(np.arange(21, 40), size=5, replace=False)):
+        delays[k] = d
+    return [2] + delays.tolist()
+
+
+@pytest.mark.parametrize("seed", range(8 + len(LONG_DELAY_HORIZONS)))
 def test_prepare_plan(seed):
     rng = np.random.RandomState(seed)
-    T = int(rng.randint(1, 60))
-    delays = [2] + rng.randint(0, 1 + int(rng.randint(1, 10)), size=T).tolist()
+    if seed < 8:
+        T = int(rng.randint(1, 60))
+        delays = [2] + rng.randint(0, 1 + int(rng.randint(1, 10)), size=T).tolist()
+    else:
+        T = LONG_DELAY_HORIZONS[seed - 8]
+        delays = _long_delays(rng, T)
     rc, plan, R = _plan(delays, T)
     assert rc == 0
     assert plan == _expected_plan(delays, T)
@@ -320,15 +339,19 @@ def _prepare_full(delays, T, variant=1):
     return nat.lib.scg_bg_prepare(ctypes.byref(c)), list(plan), c.ring_slots
 
 
-@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("seed", range(6 + len(LONG_DELAY_HORIZONS)))
 def test_prepare_full_table(seed):
     """full_table: R = the reference's row count max(T+1, max_w(w+d_w+1)) + 1
     (beergame_env.py:46-50), slot s = week s, and the weeks that ship past the horizon are
     stored (STORE/ADD into rows > T) instead of dropped."""
     from oracle.beergame import shipment_rows
     rng = np.random.RandomState(100 + seed)
-    T = int(rng.randint(1, 40))
-    delays = [2] + rng.randint(0, 1 + int(rng.randint(1, 9)), size=T).tolist()
+    if seed < 6:
+        T = int(rng.randint(1, 40))
+        delays = [2] + rng.randint(0, 1 + int(rng.randint(1, 9)), size=T).tolist()
+    else:
+        T = LONG_DELAY_HORIZONS[seed - 6]
+        delays = _long_delays(rng, T)
     rc, plan, R = _prepare_full(delays, T)
     assert rc == 0 and R == shipment_rows(T, np.asarray(delays))
     written = set(range(1, delays[0] + 1))   # the initial pipeline, even past T (:52)

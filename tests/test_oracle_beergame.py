@@ -31,6 +31,16 @@ def test_batch_oracle_matches_reference(name):
 
 
 @pytest.mark.parametrize("name", CASES)
+def test_batch_oracle_final_table_matches_reference(name):
+    """"shipments": the absolute-week table (:46-52) after the last step, of the envs the
+    golden file recorded it for."""
+    g = load_beergame(name)
+    out = run_batch_episode(g["info"], g["demand"], g["actions"])
+    ns = g["ref_shipments"].shape[1]
+    assert ns > 0 and np.array_equal(out["shipments"][:, :ns].transpose(1, 0, 2), g["ref_shipments"][-1])
+
+
+@pytest.mark.parametrize("name", CASES)
 def test_single_env_oracle_matches_reference(name):
     g = load_beergame(name)
     T, N, L = g["actions"].shape
