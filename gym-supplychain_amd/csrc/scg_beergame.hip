@@ -77,62 +77,14 @@ __global__ __launch_bounds__(64) void bg_slab_consts_kernel(BgSlabConst* __restr
 }
 
 // ---- host helpers: run-time dispatch on the level count ----------------------------------
-int launch_reset(int L, dim3 grid, hipStream_t s, const BgArgs& a) {
-  switch (L) {
-#define X(l) case l: return bg_launch_reset<l>(grid, s, a);
-    SCG_LEVEL_CASES(X)
+// f(the launchers of level L), or the error for a level count outside the table.
+template <class F>
+int with_level(int L, F&& f) {
+#define X(l) bg_launchers<l>,
+  static const BgLaunchers* (*const kLevels[])() = {SCG_LEVEL_CASES(X)};
 #undef X
-    default: return fail(SCG_ERR_INVALID, "levels=%d outside 1..%d", L, SCG_BG_MAX_LEVELS);
-  }
-}
-
-int launch_step2(int L, dim3 grid, hipStream_t s, const BgArgs& a, const WeekInfo& wk) {
-  switch (L) {
-#define X(l) case l: return bg_launch_step2<l>(grid, s, a, wk);
-    SCG_LEVEL_CASES(X)
-#undef X
-    default: return fail(SCG_ERR_INVALID, "levels=%d outside 1..%d", L, SCG_BG_MAX_LEVELS);
-  }
-}
-
-int launch_step(int L, dim3 grid, hipStream_t s, const BgArgs& a, const WeekInfo& wk, hipEvent_t ev0,
-                hipEvent_t ev1) {
-  switch (L) {
-#define X(l) case l: return bg_launch_step<l>(grid, s, a, wk, ev0, ev1);
-    SCG_LEVEL_CASES(X)
-#undef X
-    default: return fail(SCG_ERR_INVALID, "levels=%d outside 1..%d", L, SCG_BG_MAX_LEVELS);
-  }
-}
-
-int launch_server(int L, int demand_mode, hipStream_t s, scg_bg_server_box* box, uint32_t exit_seen,
-                  uint32_t idle_ticks) {
-  switch (L) {
-#define X(l) case l: return bg_launch_server<l>(s, demand_mode, box, exit_seen, idle_ticks);
-    SCG_LEVEL_CASES(X)
-#undef X
-    default: return fail(SCG_ERR_INVALID, "levels=%d outside 1..%d", L, SCG_BG_MAX_LEVELS);
-  }
-}
-
-int launch_slab(int demand_mode, int L, dim3 grid, hipStream_t s, const SlabLaunch& a, hipEvent_t ev0,
-                hipEvent_t ev1) {
-  switch (L) {
-#define X(l) case l: return bg_launch_slab<l>(demand_mode, grid, s, a, ev0, ev1);
-    SCG_LEVEL_CASES(X)
-#undef X
-    default: return fail(SCG_ERR_INVALID, "levels=%d outside 1..%d", L, SCG_BG_MAX_LEVELS);
-  }
-}
-
-int launch_rollout(int L, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, const RolloutWeeks& weeks,
-                   const int32_t* acts, int32_t* obs, int32_t* rew) {
-  switch (L) {
-#define X(l) case l: return bg_launch_rollout<l>(grid, s, a, K, weeks, acts, obs, rew);
-    SCG_LEVEL_CASES(X)
-#undef X
-    default: return fail(SCG_ERR_INVALID, "levels=%d outside 1..%d", L, SCG_BG_MAX_LEVELS);
-  }
+  if (L < 1 || L > SCG_BG_MAX_LEVELS) return fail(SCG_ERR_INVALID, "levels=%d outside 1..%d", L, SCG_BG_MAX_LEVELS);
+  return f(*kLevels[L - 1]());
 }
 
 // Word offsets of a state slab (scg_bg_slab_layout); the slab kernel derives the same ones
@@ -140,7 +92,7 @@ int launch_rollout(int L, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, 
 int slab_layout(int L, int64_t N, int32_t R, int32_t T, bool history, int64_t* off) {
   const int64_t NL = N * L;
   if (NL % 4 != 0) return fail(SCG_ERR_INVALID, "slab layout needs n_envs * levels %% 4 == 0 (got %lld)", (long long)NL);
-  if (R < 1 || R > 127) return fail(SCG_ERR_INVALID, "slab layout needs 1 <= ring_slots <= 127");
+  if (R < 1 || R > static_cast<int32_t>(kSlabRingMax)) return fail(SCG_ERR_INVALID, "slab layout needs 1 <= ring_slots <= 127");
   off[SCG_SLAB_ERROR] = 0;
   for (int f = 0; f < 6; ++f) off[SCG_SLAB_INVENTORY + f] = kSlabHeader + f * NL;
   off[SCG_SLAB_RING] = kSlabHeader + 6 * NL;
@@ -196,9 +148,26 @@ inline int32_t init_slots(const scg_bg_config* cfg) {
   return cfg->full_table ? d0 : std::min(d0, cfg->max_weeks);
 }
 
+// The launch constants BgArgs and BgSlabConst both carry, under the same names.
+template <class Consts>
+void fill_shared_consts(Consts& c, const scg_bg_config* cfg, const scg_bg_state* st) {
+  c.h = cfg->inv_cost;
+  c.b = cfg->backlog_cost;
+  c.guard = week_guard(cfg->levels, cfg->inv_cost, cfg->backlog_cost);
+  c.demand_lo = cfg->demand_lo;
+  c.demand_hi = cfg->demand_hi;
+  c.ship_value = cfg->initial_shipment_value;
+  c.orders_value = cfg->initial_orders_value;
+  c.init_slots = init_slots(cfg);
+  c.err_host = st->error_host;
+  c.demand_table = cfg->demand_table;
+  for (int l = 0; l < cfg->levels; ++l) c.init_inv[l] = cfg->initial_inventory[l];
+}
+
 BgArgs make_args(const scg_bg_config* cfg, const scg_bg_state* st) {
   BgArgs a;
   std::memset(&a, 0, sizeof(a));
+  fill_shared_consts(a, cfg, st);
   a.inv = st->inventory;
   a.bk = st->backlog;
   a.op = st->orders_placed;
@@ -208,7 +177,6 @@ BgArgs make_args(const scg_bg_config* cfg, const scg_bg_state* st) {
   a.hist = st->orders_history;
   a.ep_ret = st->episode_return;
   a.final_ret = st->final_return;
-  a.demand_table = cfg->demand_table;
   a.pthr = cfg->poisson_thresholds;
   a.n = st->n_envs;
   a.env_offset = st->env_offset;
@@ -217,19 +185,9 @@ BgArgs make_args(const scg_bg_config* cfg, const scg_bg_state* st) {
   a.episode = st->episode;
   a.demand_mode = cfg->demand_mode;
   a.pthr_len = cfg->poisson_len;
-  a.h = cfg->inv_cost;
-  a.b = cfg->backlog_cost;
-  a.ship_value = cfg->initial_shipment_value;
-  a.orders_value = cfg->initial_orders_value;
-  a.init_slots = init_slots(cfg);
   a.ring_slots = cfg->ring_slots;
-  for (int l = 0; l < cfg->levels; ++l) a.init_inv[l] = cfg->initial_inventory[l];
-  a.demand_lo = cfg->demand_lo;
-  a.demand_hi = cfg->demand_hi;
   a.max_weeks = cfg->max_weeks;
   a.err = st->error_flags;
-  a.guard = week_guard(cfg->levels, cfg->inv_cost, cfg->backlog_cost);
-  a.err_host = st->error_host;
   if (cfg->variant == 2) {
     a.pen_acc = st->penalty_costs;
     a.max_stock = cfg->max_stock;
@@ -248,20 +206,10 @@ inline dim3 grid_for(int64_t n) { return dim3(static_cast<unsigned>((n + kBlock 
 BgSlabConst slab_consts(const scg_bg_config* cfg, const scg_bg_state* st) {
   BgSlabConst v;
   std::memset(&v, 0, sizeof(v));
+  fill_shared_consts(v, cfg, st);
   v.env_base = static_cast<uint32_t>(st->env_offset);
   v.pthr_len = cfg->demand_mode == SCG_DEMAND_POISSON ? cfg->poisson_len : 0;
-  v.h = cfg->inv_cost;
-  v.b = cfg->backlog_cost;
-  v.guard = week_guard(cfg->levels, cfg->inv_cost, cfg->backlog_cost);
-  v.demand_lo = cfg->demand_lo;
-  v.demand_hi = cfg->demand_hi;
-  v.ship_value = cfg->initial_shipment_value;
-  v.orders_value = cfg->initial_orders_value;
-  v.init_slots = init_slots(cfg);
-  v.err_host = st->error_host;
-  v.demand_table = cfg->demand_table;
   v.pthr = cfg->demand_mode == SCG_DEMAND_POISSON ? cfg->poisson_thresholds : nullptr;
-  for (int l = 0; l < cfg->levels; ++l) v.init_inv[l] = cfg->initial_inventory[l];
   return v;
 }
 
@@ -377,7 +325,7 @@ int scg_bg_prepare(scg_bg_config* cfg) {
       mode = MODE_STORE;
       written[w + d] = 1;
     }
-    cfg->plan[w] = mode | (written[w] ? PLAN_ARRIVE : 0) | (d << kPlanDelayShift);
+    cfg->plan[w] = plan_word(mode, written[w] != 0, d);
   }
   cfg->ring_slots = R;
   return SCG_OK;
@@ -396,7 +344,10 @@ int scg_bg_reset(const scg_bg_config* cfg, scg_bg_state* st, int32_t* obs, void*
   if (st->week >= 0) st->episode += 1;  // the previous episode (finished or not) is discarded
   BgArgs a = make_args(cfg, st);
   a.obs = obs;
-  if (int rc = launch_reset(cfg->levels, grid_for(st->n_envs), static_cast<hipStream_t>(stream), a)) return rc;
+  if (int rc = with_level(cfg->levels, [&](const BgLaunchers& k) {
+        return k.reset(grid_for(st->n_envs), static_cast<hipStream_t>(stream), a);
+      }))
+    return rc;
   st->week = 0;
   return SCG_OK;
 }
@@ -412,8 +363,18 @@ static scg::WeekInfo week_info(const scg_bg_config* cfg, int32_t w, uint32_t fla
   wk.mode = plan_mode(p);
   wk.demand_fixed = cfg->demand_mode == SCG_DEMAND_FIXED ? cfg->customer_demand[w - 1] : 0;
   const bool terminal = (w == cfg->max_weeks);
-  wk.flags = (terminal ? 1 : 0) | ((terminal && (flags & SCG_BG_AUTORESET)) ? 2 : 0);
+  wk.flags = (terminal ? WEEK_TERMINAL : 0) | ((terminal && (flags & SCG_BG_AUTORESET)) ? WEEK_AUTORESET : 0);
   return wk;
+}
+
+// The host's week and episode counters after week wk.
+static void advance_week(scg_bg_state* st, const WeekInfo& wk) {
+  if (wk.flags & WEEK_AUTORESET) {
+    st->week = 0;
+    st->episode += 1;
+  } else {
+    st->week = wk.week;
+  }
 }
 
 static int check_step(const scg_bg_config* cfg, const scg_bg_state* st) {
@@ -437,48 +398,31 @@ int scg_bg_step_timed(const scg_bg_config* cfg, scg_bg_state* st, const int32_t*
   if (int rc = check_step(cfg, st)) return rc;
   const int32_t w = st->week + 1;
   const WeekInfo wk = week_info(cfg, w, flags);
+  const dim3 grid = grid_for(st->n_envs);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipEvent_t ev0 = static_cast<hipEvent_t>(start_event), ev1 = static_cast<hipEvent_t>(stop_event);
   if (slab_ready(cfg, st, obs, reward, terminal_obs)) {
-    if (int rc = sync_slab_consts(cfg, st, static_cast<hipStream_t>(stream))) return rc;
-    uint32_t wpack = pack_week_slab(wk);  // R <= 127 (slab_layout)
-    wpack |= (wk.flags & 1) ? SW_TERMINAL : 0u;
-    wpack |= (wk.flags & 2) ? SW_AUTORESET : 0u;
-    wpack |= st->inventory_costs ? SW_LEDGERS : 0u;
-    wpack |= st->episode_return ? SW_RETURNS : 0u;
-    wpack |= st->orders_history ? SW_HISTORY : 0u;
-    wpack |= static_cast<uint32_t>(cfg->ring_slots) << 24;
+    if (int rc = sync_slab_consts(cfg, st, s)) return rc;
+    const uint32_t wpack = pack_week_slab(wk, cfg->ring_slots, st->inventory_costs != nullptr,  // R <= 127 (slab_layout)
+                                          st->episode_return != nullptr, st->orders_history != nullptr);
     const SlabLaunch sl{st->slab, action, obs, static_cast<const BgSlabConst*>(st->step_consts), st->seed,
                         static_cast<uint32_t>(st->n_envs), wpack, static_cast<uint32_t>(w), st->episode,
                         wk.demand_fixed};
-    if (int rc = launch_slab(cfg->demand_mode, cfg->levels, grid_for(st->n_envs), static_cast<hipStream_t>(stream), sl,
-                             static_cast<hipEvent_t>(start_event), static_cast<hipEvent_t>(stop_event)))
+    if (int rc = with_level(cfg->levels, [&](const BgLaunchers& k) { return k.slab(cfg->demand_mode, grid, s, sl, ev0, ev1); }))
       return rc;
-    if (wk.flags & 2) {
-      st->week = 0;
-      st->episode += 1;
-    } else {
-      st->week = w;
-    }
-    if (done) *done = (wk.flags & 1) ? 1 : 0;
-    return SCG_OK;
-  }
-  BgArgs a = make_args(cfg, st);
-  a.act = action;
-  a.obs = obs;
-  a.rew = reward;
-  a.term_obs = terminal_obs;
-  if (cfg->variant == 2) {
-    if (int rc = launch_step2(cfg->levels, grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, wk)) return rc;
-  } else if (int rc = launch_step(cfg->levels, grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, wk,
-                                  static_cast<hipEvent_t>(start_event), static_cast<hipEvent_t>(stop_event))) {
-    return rc;
-  }
-  if (wk.flags & 2) {
-    st->week = 0;
-    st->episode += 1;
   } else {
-    st->week = w;
+    BgArgs a = make_args(cfg, st);
+    a.act = action;
+    a.obs = obs;
+    a.rew = reward;
+    a.term_obs = terminal_obs;
+    if (int rc = with_level(cfg->levels, [&](const BgLaunchers& k) {
+          return cfg->variant == 2 ? k.step2(grid, s, a, wk) : k.step(grid, s, a, wk, ev0, ev1);
+        }))
+      return rc;
   }
-  if (done) *done = (wk.flags & 1) ? 1 : 0;
+  advance_week(st, wk);
+  if (done) *done = (wk.flags & WEEK_TERMINAL) ? 1 : 0;
   return SCG_OK;
 }
 
@@ -510,8 +454,9 @@ static const ServerNames kServerNames{"step server", "the wave's stream", "wave"
 // Launch the wave (lock held). It serves, first, every slot whose request is newer than its answer.
 static int server_launch_locked(scg_bg_server* sv) {
   return server_launch(sv, [sv](uint32_t exit_seen, uint32_t idle_ticks) {
-    return launch_server(sv->levels, sv->demand_mode, static_cast<hipStream_t>(sv->stream), sv->box_dev, exit_seen,
-                         idle_ticks);
+    return with_level(sv->levels, [&](const BgLaunchers& k) {
+      return k.server(static_cast<hipStream_t>(sv->stream), sv->demand_mode, sv->box_dev, exit_seen, idle_ticks);
+    });
   });
 }
 
@@ -630,7 +575,7 @@ int scg_bg_server_post(const scg_bg_config* cfg, scg_bg_state* st, scg_bg_server
   server_publish(reinterpret_cast<uint32_t*>(&b->req[k]), line);
   slot->seq = seq;
   slot->week = w;
-  slot->done = (wk.flags & 1) ? 1 : 0;
+  slot->done = (wk.flags & WEEK_TERMINAL) ? 1 : 0;
   sv->last_ns = mono_ns();
   if (!sv->running)
     if (int rc = server_launch_locked(sv)) return rc;
@@ -674,19 +619,14 @@ int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, 
     scg_bg_state probe = *st;
     BgArgs a = make_args(cfg, st);
     while (K < SCG_BG_ROLLOUT_MAX && done_k + K < n_weeks) {
-      const int32_t w = probe.week + 1;
-      weeks.wk[K] = week_info(cfg, w, flags);
-      if (weeks.wk[K].flags & 2) {
-        probe.week = 0;
-        probe.episode += 1;
-      } else {
-        probe.week = w;
-      }
+      weeks.wk[K] = week_info(cfg, probe.week + 1, flags);
+      advance_week(&probe, weeks.wk[K]);
       ++K;
     }
-    if (int rc = launch_rollout(cfg->levels, grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, K, weeks,
-                                actions + done_k * stride, obs ? obs + done_k * stride : nullptr,
-                                rewards ? rewards + done_k * st->n_envs : nullptr))
+    if (int rc = with_level(cfg->levels, [&](const BgLaunchers& k) {
+          return k.rollout(grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, K, weeks, actions + done_k * stride,
+                           obs ? obs + done_k * stride : nullptr, rewards ? rewards + done_k * st->n_envs : nullptr);
+        }))
       return rc;
     st->week = probe.week;
     st->episode = probe.episode;

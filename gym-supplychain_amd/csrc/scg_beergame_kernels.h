@@ -28,7 +28,9 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
+#include "scg_bg_plan.h"
 #include "scg_common.h"
 #include "scg_mailbox.h"
 #include "scg_const.h"
@@ -36,16 +38,6 @@
 #include "scgpu.h"
 
 namespace scg {
-
-// ---- per-week plan word (host computed, uniform per launch) -------------------------
-enum : int32_t { MODE_DIRECT = 0, MODE_STORE = 1, MODE_ADD = 2, MODE_DROP = 3 };
-constexpr int32_t PLAN_ARRIVE = 4;
-inline int32_t plan_mode(int32_t p) { return p & 3; }
-inline bool plan_arrive(int32_t p) { return (p & PLAN_ARRIVE) != 0; }
-// bits 8 and up hold the week's whole delay (the word is non-negative)
-constexpr int kPlanDelayShift = 8;
-static_assert(static_cast<int64_t>(SCG_BG_MAX_DELAY) << kPlanDelayShift <= INT32_MAX, "plan delay field too narrow");
-inline int32_t plan_delay(int32_t p) { return p >> kPlanDelayShift; }
 
 constexpr int kBlock = 256;
 
@@ -282,15 +274,6 @@ __global__ __launch_bounds__(kBlock) void bg_reset_kernel(const BgArgs a) {
 // comes back as the row scheduled `delay` weeks ahead (or is already added into the
 // inventory when the week's delay is 0, `direct`). Shared by the step kernel (state
 // from/to HBM every launch) and the rollout kernel (state held in registers).
-struct WeekInfo {
-  int32_t week;        // 1..T
-  int32_t read_slot;   // -1: nothing due
-  int32_t write_slot;
-  int32_t mode;        // MODE_*
-  int32_t demand_fixed;
-  int32_t flags;       // bit0 terminal, bit1 autoreset
-};
-
 template <int L>
 __device__ __forceinline__ int32_t step_core(int32_t h, int32_t b, int32_t demand, bool direct,
                                              const int32_t (&due)[L], int32_t (&inv)[L], int32_t (&bk)[L],
@@ -454,23 +437,6 @@ __device__ __forceinline__ void zero_row(int32_t (&v)[L]) {
   for (int l = 0; l < L; ++l) v[l] = 0;
 }
 
-// Week plan packed into one dword for the step kernel's preloaded arguments:
-// bits 0-13 read_slot + 1 (0: nothing due), 14-27 write_slot, 28-29 mode, 30-31 flags
-// (slots < 2^14 > SCG_BG_MAX_WEEKS + SCG_BG_MAX_DELAY + 2, the longest full table).
-constexpr uint32_t kWeekSlotBits = 14, kWeekSlotMask = (1u << kWeekSlotBits) - 1;
-static_assert(SCG_BG_MAX_WEEKS + SCG_BG_MAX_DELAY + 2 < (1 << kWeekSlotBits), "ring slot field too narrow");
-inline uint32_t pack_week(const WeekInfo& wk) {
-  return static_cast<uint32_t>(wk.read_slot + 1) | (static_cast<uint32_t>(wk.write_slot) << kWeekSlotBits) |
-         (static_cast<uint32_t>(wk.mode) << 28) | (static_cast<uint32_t>(wk.flags) << 30);
-}
-
-// The slab kernel's week plan (its ring has at most 127 slots, scg_bg_slab_layout): bits 0-7
-// read_slot + 1, 8-15 write_slot, 16-17 mode; the launcher adds the SW_* option bits and R.
-inline uint32_t pack_week_slab(const WeekInfo& wk) {
-  return static_cast<uint32_t>(wk.read_slot + 1) | (static_cast<uint32_t>(wk.write_slot) << 8) |
-         (static_cast<uint32_t>(wk.mode) << 16);
-}
-
 // step(action) for one env per lane: every row this launch reads is loaded up front (one
 // round of memory latency), the week is computed in registers, then every row is stored.
 // The leading scalar arguments (the four state rows' and the ring's base pointers, the env
@@ -486,11 +452,9 @@ __device__ __forceinline__ void bg_step_env(int64_t n, int32_t* __restrict__ inv
                                             int32_t* __restrict__ op_p, const int32_t* __restrict__ act_p,
                                             int32_t* __restrict__ ring_p, uint32_t n32, uint32_t wpack,
                                             const BgArgs& a, const WeekInfo& wk, const int32_t* act_in = nullptr) {
-  const int32_t read_slot = static_cast<int32_t>(wpack & kWeekSlotMask) - 1;
-  const int32_t write_slot = static_cast<int32_t>((wpack >> kWeekSlotBits) & kWeekSlotMask);
-  const int32_t mode = static_cast<int32_t>((wpack >> 28) & 3u);
-  const bool terminal = wpack & (1u << 30);
-  const bool autoreset = wpack & (2u << 30);
+  const WeekPlan p = unpack_week(wpack);
+  const int32_t read_slot = p.read_slot, write_slot = p.write_slot, mode = p.mode;
+  const bool terminal = p.terminal, autoreset = p.autoreset;
   const int64_t row = n * L;
   const int64_t stride = static_cast<int64_t>(n32) * L;
 
@@ -698,9 +662,6 @@ static_assert(sizeof(BgSlabConst) <= SCG_BG_STEP_CONSTS_BYTES && offsetof(BgSlab
                   offsetof(BgSlabConst, init_inv) == 64 && offsetof(BgSlabConst, thr) == 128,
               "BgSlabConst layout");
 
-// wpack bits of the slab kernel
-constexpr uint32_t SW_TERMINAL = 1u << 18, SW_AUTORESET = 1u << 19, SW_LEDGERS = 1u << 20, SW_RETURNS = 1u << 21,
-                   SW_HISTORY = 1u << 22;
 constexpr int kSlabHeader = 4;  // int32 words before the first row (the error word + padding)
 
 template <int L, int DM>
@@ -713,12 +674,10 @@ __global__ __launch_bounds__(kBlock) void bg_step_slab_kernel(int32_t* __restric
   if (n >= static_cast<int64_t>(n32)) return;
   const ConstTab<BgSlabConst> c = const_tab(consts);
   const uint32_t key0 = static_cast<uint32_t>(key), key1 = static_cast<uint32_t>(key >> 32);
-  const int32_t read_slot = static_cast<int32_t>(wpack & 0xffu) - 1;
-  const int32_t write_slot = static_cast<int32_t>((wpack >> 8) & 0xffu);
-  const int32_t mode = static_cast<int32_t>((wpack >> 16) & 3u);
-  const int32_t R = static_cast<int32_t>((wpack >> 24) & 0x7fu);
-  const bool terminal = wpack & SW_TERMINAL, autoreset = wpack & SW_AUTORESET;
-  const bool ledgers = wpack & SW_LEDGERS, returns = wpack & SW_RETURNS, history = wpack & SW_HISTORY;
+  const WeekPlan p = unpack_week_slab(wpack);
+  const int32_t read_slot = p.read_slot, write_slot = p.write_slot, mode = p.mode, R = p.R;
+  const bool terminal = p.terminal, autoreset = p.autoreset;
+  const bool ledgers = p.ledgers, returns = p.returns, history = p.history;
   const int64_t NL = static_cast<int64_t>(n32) * L;
   const int64_t row = n * L;
   int32_t* const rows = slab + kSlabHeader;           // row field f of env n: rows + f * NL + row
@@ -847,8 +806,8 @@ __global__ __launch_bounds__(kBlock) void bg2_step_kernel(const BgArgs a, const 
   if (n >= a.n) return;
   const int64_t row = n * L;
   const int64_t stride = a.n * L;
-  const bool terminal = wk.flags & 1;
-  const bool autoreset = wk.flags & 2;
+  const bool terminal = wk.flags & WEEK_TERMINAL;
+  const bool autoreset = wk.flags & WEEK_AUTORESET;
   int32_t read_slot = wk.read_slot, write_slot = wk.write_slot, mode = wk.mode;
   if (a.stochastic_delays) {
     const uint32_t u = scg::philox_word(a.key0, a.key1, static_cast<uint32_t>(a.env_offset + n), a.episode,
@@ -1033,8 +992,8 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
     }
     if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
     ret += reward;
-    if ((wk.flags & 1) && a.final_ret) a.final_ret[n] = ret;
-    if (wk.flags & 2) {  // auto-reset in registers (:140-156)
+    if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
+    if (wk.flags & WEEK_AUTORESET) {  // auto-reset in registers (:140-156)
 #pragma unroll
       for (int l = 0; l < L; ++l) {
         inv[l] = a.init_inv[l];
@@ -1121,6 +1080,18 @@ int launch_slab_module(dim3 grid, hipStream_t s, SlabLaunch a) {
   return SCG_OK;
 }
 
+// The host's way from a demand mode to a kernel instantiation:
+// f(std::integral_constant<int, DM>) for the mode's SCG_DEMAND_* (anything else counts as POISSON).
+template <class F>
+inline int dispatch_demand(int mode, F&& f) {
+  switch (mode) {
+    case SCG_DEMAND_FIXED: return f(std::integral_constant<int, SCG_DEMAND_FIXED>{});
+    case SCG_DEMAND_TABLE: return f(std::integral_constant<int, SCG_DEMAND_TABLE>{});
+    case SCG_DEMAND_UNIFORM: return f(std::integral_constant<int, SCG_DEMAND_UNIFORM>{});
+    default: return f(std::integral_constant<int, SCG_DEMAND_POISSON>{});
+  }
+}
+
 // ---- per-level launchers (explicitly instantiated in scg_bg_levels_*.hip) ---------------
 template <int L>
 int bg_launch_reset(dim3 grid, hipStream_t s, const BgArgs& a) {
@@ -1136,63 +1107,33 @@ int bg_launch_step2(dim3 grid, hipStream_t s, const BgArgs& a, const WeekInfo& w
 
 // hipExtLaunchKernelGGL ties the optional events to this dispatch's own start/end
 // timestamps (the numbers rocprofv3 reports), not to separate event packets.
-template <int L, int DM>
-int bg_launch_step_dm(dim3 grid, hipStream_t s, const BgArgs& a, const WeekInfo& wk, hipEvent_t ev0, hipEvent_t ev1) {
-  hipExtLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_kernel<L, DM>), grid, dim3(kBlock), 0, s, ev0, ev1, 0, a.inv, a.bk, a.op,
-                        a.act, a.ring, static_cast<uint32_t>(a.n), pack_week(wk), a, wk);
-  return check_launch("bg_step_kernel");
-}
-
 template <int L>
 int bg_launch_step(dim3 grid, hipStream_t s, const BgArgs& a, const WeekInfo& wk, hipEvent_t ev0, hipEvent_t ev1) {
-  switch (a.demand_mode) {
-    case SCG_DEMAND_FIXED: return bg_launch_step_dm<L, SCG_DEMAND_FIXED>(grid, s, a, wk, ev0, ev1);
-    case SCG_DEMAND_TABLE: return bg_launch_step_dm<L, SCG_DEMAND_TABLE>(grid, s, a, wk, ev0, ev1);
-    case SCG_DEMAND_UNIFORM: return bg_launch_step_dm<L, SCG_DEMAND_UNIFORM>(grid, s, a, wk, ev0, ev1);
-    default: return bg_launch_step_dm<L, SCG_DEMAND_POISSON>(grid, s, a, wk, ev0, ev1);
-  }
+  return dispatch_demand(a.demand_mode, [&](auto dm) {
+    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_kernel<L, decltype(dm)::value>), grid, dim3(kBlock), 0, s, ev0, ev1, 0,
+                          a.inv, a.bk, a.op, a.act, a.ring, static_cast<uint32_t>(a.n), pack_week(wk), a, wk);
+    return check_launch("bg_step_kernel");
+  });
 }
 
 template <int L>
 int bg_launch_server(hipStream_t s, int demand_mode, scg_bg_server_box* box, uint32_t exit_seen, uint32_t idle_ticks) {
-  switch (demand_mode) {
-    case SCG_DEMAND_FIXED:
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_server_kernel<L, SCG_DEMAND_FIXED>), dim3(1), dim3(kServerBlock), 0, s, box,
-                         exit_seen, idle_ticks);
-      break;
-    case SCG_DEMAND_TABLE:
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_server_kernel<L, SCG_DEMAND_TABLE>), dim3(1), dim3(kServerBlock), 0, s, box,
-                         exit_seen, idle_ticks);
-      break;
-    case SCG_DEMAND_UNIFORM:
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_server_kernel<L, SCG_DEMAND_UNIFORM>), dim3(1), dim3(kServerBlock), 0, s, box,
-                         exit_seen, idle_ticks);
-      break;
-    default:
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_server_kernel<L, SCG_DEMAND_POISSON>), dim3(1), dim3(kServerBlock), 0, s, box,
-                         exit_seen, idle_ticks);
-  }
-  return check_launch("bg_server_kernel");
-}
-
-template <int L, int DM>
-int bg_launch_slab_dm(dim3 grid, hipStream_t s, const SlabLaunch& a, hipEvent_t ev0, hipEvent_t ev1) {
-  if (ev0 || ev1) {
-    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_slab_kernel<L, DM>), grid, dim3(kBlock), 0, s, ev0, ev1, 0, a.slab,
-                          a.act, a.out, a.consts, a.key, a.n32, a.wpack, a.week, a.episode, a.demand_fixed);
-    return check_launch("bg_step_slab_kernel");
-  }
-  return launch_slab_module<L, DM>(grid, s, a);
+  return dispatch_demand(demand_mode, [&](auto dm) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_server_kernel<L, decltype(dm)::value>), dim3(1), dim3(kServerBlock), 0, s, box,
+                       exit_seen, idle_ticks);
+    return check_launch("bg_server_kernel");
+  });
 }
 
 template <int L>
 int bg_launch_slab(int demand_mode, dim3 grid, hipStream_t s, const SlabLaunch& a, hipEvent_t ev0, hipEvent_t ev1) {
-  switch (demand_mode) {
-    case SCG_DEMAND_FIXED: return bg_launch_slab_dm<L, SCG_DEMAND_FIXED>(grid, s, a, ev0, ev1);
-    case SCG_DEMAND_TABLE: return bg_launch_slab_dm<L, SCG_DEMAND_TABLE>(grid, s, a, ev0, ev1);
-    case SCG_DEMAND_UNIFORM: return bg_launch_slab_dm<L, SCG_DEMAND_UNIFORM>(grid, s, a, ev0, ev1);
-    default: return bg_launch_slab_dm<L, SCG_DEMAND_POISSON>(grid, s, a, ev0, ev1);
-  }
+  return dispatch_demand(demand_mode, [&](auto dm) {
+    constexpr int DM = decltype(dm)::value;
+    if (!ev0 && !ev1) return launch_slab_module<L, DM>(grid, s, a);
+    hipExtLaunchKernelGGL(HIP_KERNEL_NAME(bg_step_slab_kernel<L, DM>), grid, dim3(kBlock), 0, s, ev0, ev1, 0, a.slab,
+                          a.act, a.out, a.consts, a.key, a.n32, a.wpack, a.week, a.episode, a.demand_fixed);
+    return check_launch("bg_step_slab_kernel");
+  });
 }
 
 template <int L>
@@ -1207,17 +1148,27 @@ int bg_launch_rollout(dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, cons
   return check_launch("bg_rollout_kernel");
 }
 
+// One level's six launchers; scg_beergame.hip keeps a table of them by L.
+struct BgLaunchers {
+  int (*reset)(dim3, hipStream_t, const BgArgs&);
+  int (*step2)(dim3, hipStream_t, const BgArgs&, const WeekInfo&);
+  int (*step)(dim3, hipStream_t, const BgArgs&, const WeekInfo&, hipEvent_t, hipEvent_t);
+  int (*server)(hipStream_t, int, scg_bg_server_box*, uint32_t, uint32_t);
+  int (*slab)(int, dim3, hipStream_t, const SlabLaunch&, hipEvent_t, hipEvent_t);
+  int (*rollout)(dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&, const int32_t*, int32_t*, int32_t*);
+};
+
+template <int L>
+const BgLaunchers* bg_launchers() {
+  static const BgLaunchers k{bg_launch_reset<L>, bg_launch_step2<L>, bg_launch_step<L>,
+                             bg_launch_server<L>, bg_launch_slab<L>, bg_launch_rollout<L>};
+  return &k;
+}
+
 #define SCG_LEVEL_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 
 // Explicit instantiation (definition or, with `extern`, declaration) of level l's launchers.
-#define SCG_BG_LAUNCHERS(EXT, l)                                                                                     \
-  EXT template int bg_launch_reset<l>(dim3, hipStream_t, const BgArgs&);                                            \
-  EXT template int bg_launch_step2<l>(dim3, hipStream_t, const BgArgs&, const WeekInfo&);                           \
-  EXT template int bg_launch_step<l>(dim3, hipStream_t, const BgArgs&, const WeekInfo&, hipEvent_t, hipEvent_t);    \
-  EXT template int bg_launch_server<l>(hipStream_t, int, scg_bg_server_box*, uint32_t, uint32_t);                   \
-  EXT template int bg_launch_slab<l>(int, dim3, hipStream_t, const SlabLaunch&, hipEvent_t, hipEvent_t);            \
-  EXT template int bg_launch_rollout<l>(dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&,             \
-                                        const int32_t*, int32_t*, int32_t*);
+#define SCG_BG_LAUNCHERS(EXT, l) EXT template const BgLaunchers* bg_launchers<l>();
 #define SCG_BG_EXTERN_LEVEL(l) SCG_BG_LAUNCHERS(extern, l)
 SCG_LEVEL_CASES(SCG_BG_EXTERN_LEVEL)
 #undef SCG_BG_EXTERN_LEVEL

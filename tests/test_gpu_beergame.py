@@ -392,10 +392,18 @@ def test_slab_and_general_kernels_agree():
     kw = dict(demand="poisson", seed=seed, device=DEV, track_history=True)
     a = BeerGameVecEnv(N, info, **kw)
     b = BeerGameVecEnv(N, info, state_slab=False, **kw)
+    _step_pair(a, b, acts)
+
+
+def _step_pair(a, b, acts):
+    """Steps the slab env a and the separate-buffers env b through acts, comparing every output
+    and every state tensor after each step. Returns a's (obs, reward, all done) per step as host
+    values; a terminal step's obs is its terminal observation."""
     assert a._slab is not None and b._slab is None
     a.reset()
     b.reset()
-    for k in range(2 * T + 3):
+    seen = []
+    for k in range(acts.shape[0]):
         oa, ra, da, ia = a.step(acts[k])
         ob, rb, db, ib = b.step(acts[k])
         assert torch.equal(oa, ob) and torch.equal(ra, rb) and torch.equal(da, db), k
@@ -406,8 +414,46 @@ def test_slab_and_general_kernels_agree():
                   "all_orders_placed"):
             assert torch.equal(getattr(a, t), getattr(b, t)), (k, t)
         assert torch.equal(a._ring, b._ring), k
+        seen.append(((ia["terminal_observation"] if ia else oa).cpu().numpy(), ra.cpu().numpy(), bool(da.all())))
     a.check_errors()
     b.check_errors()
+    return seen
+
+
+@pytest.mark.parametrize("demand", ["fixed", "poisson", "table"])
+@pytest.mark.parametrize("N,L", [(260, 4), (12, 3), (6, 2), (8, 1)])
+def test_slab_and_general_kernels_agree_at_small_shapes(N, L, demand):
+    """The same pair at the shapes where a row path changes: a full block plus a 4-lane tail
+    (260, 4), scalar rows (12, 3), int2 rows (6, 2), a single level (8, 1); every N * L is a
+    multiple of 4, so the first env does run the slab kernel. Six weeks whose delays ship
+    direct (0), twice into one arrival week (weeks 1 and 2 into week 4: store, then accumulate)
+    and past the horizon (weeks 5 and 6: drop), with ledgers, returns and history on, over
+    2 T + 3 steps (two auto-resets). The first episode is also held against the NumPy oracle."""
+    from gym_supplychain_amd import BeerGameVecEnv
+    T, seed, lam = 6, 31, 8.0
+    info = dict(levels=L, initial_inventory=[12, 9, 7, 5][:L], shipment_delays=[3, 2, 0, 1, 4, 1])
+    acts_np = _uniform_actions_np(seed, N, 2 * T + 3, L, 1, -2, 9)
+    kw = dict(seed=seed, device=DEV, track_history=True)
+    if demand == "fixed":
+        info["customer_demand"] = [4, 0, 9, 2, 7, 5]
+        dem_np = np.tile(np.asarray(info["customer_demand"], dtype=np.int64), (N, 1))
+        kw["demand"] = "fixed"
+    elif demand == "poisson":
+        words = draw_words(seed, np.arange(N), 0, T, STREAM_DEMAND)
+        dem_np = poisson_invert(words, poisson_thresholds(lam))
+        kw.update(demand="poisson", poisson_lambda=lam, horizon=T)
+    else:
+        dem_np = (np.arange(N)[:, None] * 7 + np.arange(T)[None, :] * 3) % 11
+        kw["demand"] = _i32(dem_np.T)
+    a = BeerGameVecEnv(N, info, **kw)
+    b = BeerGameVecEnv(N, info, state_slab=False, **kw)
+    seen = _step_pair(a, b, _i32(acts_np))
+    want = run_batch_episode(info, dem_np, acts_np[:T])
+    for w in range(T):
+        obs, rew, done = seen[w]
+        assert np.array_equal(obs, want["obs"][w]) and np.array_equal(rew, want["reward"][w]), w
+        assert done == (w == T - 1)
+    assert a.week == 3 and a.episode == 2
 
 
 @pytest.mark.parametrize("N,L", [(77, 3), (1001, 5)])
