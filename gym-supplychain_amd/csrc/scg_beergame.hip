@@ -605,7 +605,6 @@ int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, 
                    int32_t* obs, int32_t* rewards, uint32_t flags, void* stream) {
   if (int rc = check_state(cfg, st)) return rc;
   if (!actions || n_weeks < 0) return fail(SCG_ERR_INVALID, "rollout needs actions and n_weeks >= 0");
-  if (cfg->variant == 2) return fail(SCG_ERR_INVALID, "rollout is not implemented for BeerGameEnv2");
   if (int rc = check_step(cfg, st)) return rc;
   if (!(flags & SCG_BG_AUTORESET) && st->week + static_cast<int64_t>(n_weeks) > cfg->max_weeks)
     return fail(SCG_ERR_PAST_HORIZON, "rollout of %d weeks from week %d passes the terminal week %d", n_weeks,
@@ -624,8 +623,9 @@ int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, 
       ++K;
     }
     if (int rc = with_level(cfg->levels, [&](const BgLaunchers& k) {
-          return k.rollout(grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, K, weeks, actions + done_k * stride,
-                           obs ? obs + done_k * stride : nullptr, rewards ? rewards + done_k * st->n_envs : nullptr);
+          const auto launch = cfg->variant == 2 ? k.rollout2 : k.rollout;
+          return launch(grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, K, weeks, actions + done_k * stride,
+                        obs ? obs + done_k * stride : nullptr, rewards ? rewards + done_k * st->n_envs : nullptr);
         }))
       return rc;
     st->week = probe.week;

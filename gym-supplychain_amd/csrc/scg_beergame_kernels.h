@@ -1055,6 +1055,197 @@ __global__ __launch_bounds__(kBlock) void bg_rollout_lds_kernel(const BgArgs a, 
   }
 }
 
+// ---- BeerGameEnv2 rollout ---------------------------------------------------------------
+// One BeerGameEnv2 week of one env in registers: the arithmetic of bg2_step_kernel, statement
+// for statement (int64 as the reference computes it, every stored value checked against
+// int32). A second copy on purpose: bg2_step_kernel keeps its own body, so its generated code
+// stays what it was (DESIGN §6.1 on what a shared body cost the slab kernel's schedule).
+template <int L>
+__device__ __forceinline__ int32_t week2_update(const BgArgs& a, int32_t demand, bool direct, const int32_t (&due)[L],
+                                                int32_t (&inv)[L], int32_t (&bk)[L], int32_t (&op)[L],
+                                                const int32_t (&act)[L], int32_t (&ship)[L], int32_t (&obs)[L],
+                                                int32_t (&iacc)[L], int32_t (&bacc)[L], int32_t (&pacc)[L], bool& ovf) {
+  int64_t inc[L], iv[L], fill[L], del[L], sh[L];
+  inc[0] = demand;
+#pragma unroll
+  for (int l = 1; l < L; ++l) inc[l] = op[l - 1];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    iv[l] = static_cast<int64_t>(inv[l]) + due[l];
+    fill[l] = inc[l] + bk[l];
+    del[l] = iv[l] < fill[l] ? iv[l] : fill[l];
+  }
+#pragma unroll
+  for (int l = 0; l + 1 < L; ++l) sh[l] = del[l + 1];
+  sh[L - 1] = op[L - 1];
+  int64_t cost = 0, pen = 0;
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    iv[l] += (direct ? sh[l] : 0) - del[l];
+    const int64_t b64 = fill[l] - del[l];
+    const int64_t ob = static_cast<int64_t>(a.max_stock) + iv[l] - b64;
+    const int64_t over = (iv[l] > a.max_stock ? iv[l] - a.max_stock : 0) + (b64 > a.max_stock ? b64 - a.max_stock : 0);
+    const int64_t i_c = static_cast<int64_t>(a.h) * iv[l], b_c = static_cast<int64_t>(a.b) * b64;
+    const int64_t p_c = static_cast<int64_t>(a.penalty) * over;
+    const int64_t ia = iacc[l] + i_c, ba = bacc[l] + b_c, pa = pacc[l] + p_c;
+    cost += i_c + b_c;
+    pen += p_c;
+    ovf |= out32(iv[l]) | out32(b64) | out32(ob) | out32(sh[l]) | out32(ia) | out32(ba) | out32(pa);
+    inv[l] = static_cast<int32_t>(iv[l]);
+    bk[l] = static_cast<int32_t>(b64);
+    op[l] = act[l];                                   // absolute orders (:168)
+    obs[l] = static_cast<int32_t>(ob);
+    ship[l] = static_cast<int32_t>(sh[l]);
+    iacc[l] = static_cast<int32_t>(ia);
+    bacc[l] = static_cast<int32_t>(ba);
+    pacc[l] = static_cast<int32_t>(pa);
+  }
+  const int64_t reward64 = -cost - pen;               // :177-180
+  ovf |= out32(reward64);
+  return static_cast<int32_t>(reward64);
+}
+
+// K BeerGameEnv2 weeks per launch: inventory, backlog, orders, the three ledgers and the
+// return stay in registers; per week the action row comes in and the obs / reward (and
+// history) rows go out, 36 B per env-week at L = 4, and everything else is written once at
+// the end. With a delay list the host's weeks give the ring slots and modes, as in
+// rollout_body; with stochastic delays each lane draws its own week's delay under the
+// in-register episode, clears the slot it received and read-modify-writes the slot it ships
+// into, so slots differ between lanes: both ring views take a per-lane slot (in LDS a lane
+// only ever touches its own column, whatever the slot).
+// An auto-reset inside the launch is reset_env on the ring view and the registers.
+template <int L, class Ring>
+__device__ __forceinline__ void rollout2_body(const BgArgs& a, int64_t n, int32_t K, const RolloutWeeks& weeks,
+                                              const int32_t* __restrict__ acts, int32_t* __restrict__ obs_out,
+                                              int32_t* __restrict__ rew_out, const Ring& ring) {
+  const int64_t row = n * L;
+  const int64_t stride = a.n * L;
+  int32_t inv[L], bk[L], op[L], iacc[L], bacc[L], pacc[L];
+  load_row<L>(a.inv + row, inv);
+  load_row<L>(a.bk + row, bk);
+  load_row<L>(a.op + row, op);
+  zero_row<L>(iacc);
+  zero_row<L>(bacc);
+  zero_row<L>(pacc);
+  if (a.inv_acc) load_row<L>(a.inv_acc + row, iacc);
+  if (a.bk_acc) load_row<L>(a.bk_acc + row, bacc);
+  if (a.pen_acc) load_row<L>(a.pen_acc + row, pacc);
+  int64_t ret = a.ep_ret ? a.ep_ret[n] : 0;
+  uint32_t episode = a.episode;
+  bool ovf = false;
+  for (int32_t k0 = 0; k0 < K; k0 += kRolloutGroup) {
+  int32_t group_act[kRolloutGroup][L];
+#pragma unroll
+  for (int u = 0; u < kRolloutGroup; ++u)
+    if (k0 + u < K) load_row<L>(acts + (k0 + u) * stride + row, group_act[u]);
+#pragma unroll
+  for (int u = 0; u < kRolloutGroup; ++u) {
+    const int32_t k = k0 + u;
+    if (k >= K) break;
+    const WeekInfo wk = weeks.wk[k];
+    const bool autoreset = wk.flags & WEEK_AUTORESET;
+    int32_t read_slot = wk.read_slot, write_slot = wk.write_slot, mode = wk.mode;
+    if (a.stochastic_delays) {
+      const uint32_t w = scg::philox_word(a.key0, a.key1, static_cast<uint32_t>(a.env_offset + n), episode,
+                                          static_cast<uint32_t>(wk.week - 1), SCG_STREAM_BG2_DELAY);
+      const int32_t d = a.delay_lo + static_cast<int32_t>((static_cast<uint64_t>(w) * static_cast<uint32_t>(a.delay_hi - a.delay_lo)) >> 32);
+      read_slot = wk.week % a.ring_slots;
+      write_slot = (wk.week + d) % a.ring_slots;
+      mode = d == 0 ? MODE_DIRECT : (wk.week + d > a.max_weeks ? MODE_DROP : MODE_ADD);
+    }
+    int32_t due[L], obs[L], ship[L], cur[L];
+    int32_t(&act)[L] = group_act[u];
+    zero_row<L>(due);
+    zero_row<L>(cur);
+    if (read_slot >= 0) ring.load(read_slot, due);
+    if (mode == MODE_ADD) ring.load(write_slot, cur);
+    if (autoreset) {  // the step kernel starts an auto-reset week's ledgers from zero (they end zeroed)
+      zero_row<L>(iacc);
+      zero_row<L>(bacc);
+      zero_row<L>(pacc);
+    }
+    const int32_t demand = a.demand_mode == SCG_DEMAND_FIXED ? wk.demand_fixed : week_demand(a, n, wk.week, episode);
+    const int32_t reward = week2_update<L>(a, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship, obs, iacc, bacc,
+                                           pacc, ovf);
+    if (a.stochastic_delays) {  // consumed: the slot is reused R weeks on
+      zero_row<L>(due);
+      ring.store(read_slot, due);
+    }
+    if (mode == MODE_STORE) {
+      ring.store(write_slot, ship);
+    } else if (mode == MODE_ADD) {
+      add_ship<L>(cur, ship, ovf);
+      ring.store(write_slot, cur);
+    }
+    if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
+    ret += reward;
+    if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
+    if (autoreset) {  // reset_env in registers and on the ring view
+      int32_t v[L];
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        inv[l] = a.init_inv[l];
+        bk[l] = 0;
+        op[l] = a.orders_value;
+        iacc[l] = bacc[l] = pacc[l] = 0;
+        obs[l] = inv[l] + a.max_stock;
+        v[l] = 0;
+      }
+      if (a.stochastic_delays)
+        for (int s = 0; s < a.ring_slots; ++s) ring.store(s, v);
+#pragma unroll
+      for (int l = 0; l < L; ++l) v[l] = a.ship_value;
+      for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, v);
+      if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
+      ret = 0;
+      ++episode;
+    }
+    if (obs_out) store_row<L>(obs_out + k * stride + row, obs);
+    if (rew_out) rew_out[k * a.n + n] = reward;
+  }
+  }
+  store_row<L>(a.inv + row, inv);
+  store_row<L>(a.bk + row, bk);
+  store_row<L>(a.op + row, op);
+  if (a.inv_acc) store_row<L>(a.inv_acc + row, iacc);
+  if (a.bk_acc) store_row<L>(a.bk_acc + row, bacc);
+  if (a.pen_acc) store_row<L>(a.pen_acc + row, pacc);
+  if (a.ep_ret) a.ep_ret[n] = ret;
+  note_overflow(a.err, ovf);
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void bg2_rollout_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
+                                                             const int32_t* __restrict__ acts, int32_t* __restrict__ obs_out,
+                                                             int32_t* __restrict__ rew_out) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (n >= a.n) return;
+  rollout2_body<L>(a, n, K, weeks, acts, obs_out, rew_out, RingHbm<L>{a.ring, a.n * L, n * L});
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void bg2_rollout_lds_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
+                                                                 const int32_t* __restrict__ acts,
+                                                                 int32_t* __restrict__ obs_out,
+                                                                 int32_t* __restrict__ rew_out) {
+  extern __shared__ int32_t lds_ring[];
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (n >= a.n) return;  // lanes only touch their own LDS column: no block barrier needed
+  const RingHbm<L> hbm{a.ring, a.n * L, n * L};
+  const RingLds<L> lds{lds_ring + threadIdx.x};
+  for (int s = 0; s < a.ring_slots; ++s) {
+    int32_t v[L];
+    hbm.load(s, v);
+    lds.store(s, v);
+  }
+  rollout2_body<L>(a, n, K, weeks, acts, obs_out, rew_out, lds);
+  for (int s = 0; s < a.ring_slots; ++s) {
+    int32_t v[L];
+    lds.load(s, v);
+    hbm.store(s, v);
+  }
+}
+
 // hipModuleLaunchKernel with the kernel's function handle resolved once per instantiation,
 // skipping the host-stub lookup of hipLaunchKernel on every step: ≈0.5 µs less host time
 // per step (tools/short_region.py, profiles/r02h_short_region.log).
@@ -1148,7 +1339,20 @@ int bg_launch_rollout(dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, cons
   return check_launch("bg_rollout_kernel");
 }
 
-// One level's six launchers; scg_beergame.hip keeps a table of them by L.
+// BeerGameEnv2's pair, by the same ring rule.
+template <int L>
+int bg_launch_rollout2(dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, const RolloutWeeks& weeks,
+                       const int32_t* acts, int32_t* obs, int32_t* rew) {
+  const size_t lds = static_cast<size_t>(a.ring_slots) * L * kBlock * sizeof(int32_t);
+  if (lds <= 64 * 1024) {
+    hipLaunchKernelGGL(bg2_rollout_lds_kernel<L>, grid, dim3(kBlock), lds, s, a, K, weeks, acts, obs, rew);
+    return check_launch("bg2_rollout_lds_kernel");
+  }
+  hipLaunchKernelGGL(bg2_rollout_kernel<L>, grid, dim3(kBlock), 0, s, a, K, weeks, acts, obs, rew);
+  return check_launch("bg2_rollout_kernel");
+}
+
+// One level's seven launchers; scg_beergame.hip keeps a table of them by L.
 struct BgLaunchers {
   int (*reset)(dim3, hipStream_t, const BgArgs&);
   int (*step2)(dim3, hipStream_t, const BgArgs&, const WeekInfo&);
@@ -1156,12 +1360,14 @@ struct BgLaunchers {
   int (*server)(hipStream_t, int, scg_bg_server_box*, uint32_t, uint32_t);
   int (*slab)(int, dim3, hipStream_t, const SlabLaunch&, hipEvent_t, hipEvent_t);
   int (*rollout)(dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&, const int32_t*, int32_t*, int32_t*);
+  int (*rollout2)(dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&, const int32_t*, int32_t*, int32_t*);
 };
 
 template <int L>
 const BgLaunchers* bg_launchers() {
   static const BgLaunchers k{bg_launch_reset<L>, bg_launch_step2<L>, bg_launch_step<L>,
-                             bg_launch_server<L>, bg_launch_slab<L>, bg_launch_rollout<L>};
+                             bg_launch_server<L>, bg_launch_slab<L>, bg_launch_rollout<L>,
+                             bg_launch_rollout2<L>};
   return &k;
 }
 

@@ -859,6 +859,13 @@ class BeerGame2VecEnv(BeerGameVecEnv):
     orders (int32 [N, L]); rewards include the capacity penalty. A (low, high)
     customer_demand or shipment_delays draws randint(low, high) per (env, episode, week)
     on device with Philox (streams 4 and 5) where the reference uses RandomState (:76-92).
+
+    rollout(actions [K, N, L]) runs K weeks in as few launches as possible, with the same
+    results as K step() calls: the actions are absolute orders, each obs row is
+    `max_stock + inventory - backlog` (the reset observation at a terminal week with
+    auto-reset) and each reward includes the capacity penalty. Random demand and delays of an
+    episode begun inside a rollout are drawn as step() would draw them. A rollout returns no
+    'terminal_observation'; check_errors() reports an int32 overflow after it.
     """
 
     def __init__(self, n_envs, max_stock=100, max_order=30, weeks=35, levels=4, customer_demand=None,
@@ -882,9 +889,6 @@ class BeerGame2VecEnv(BeerGameVecEnv):
         L = cfg.levels
         self.single_observation_space = spaces.Box(0, 2 * cfg.max_stock - 1, (L,), np.int32)   # MultiDiscrete (:28)
         self.single_action_space = spaces.Box(0, cfg.max_order - 1, (L,), np.int32)            # MultiDiscrete (:27)
-
-    def rollout(self, *a, **k):
-        raise NotImplementedError("rollout is not implemented for BeerGameEnv2")
 
 
 class BeerGameEnv2(spaces.Env):

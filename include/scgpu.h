@@ -367,9 +367,20 @@ SCG_API uint32_t scg_bg_server_line_check(const scg_bg_server_line* line);
 /*
  * K consecutive steps in one launch per <= SCG_BG_ROLLOUT_MAX weeks, state held in
  * registers/LDS (open-loop action plans, evaluation sweeps). Same results as K calls
- * of scg_bg_step with the same flags (SCG_BG_AUTORESET may cross episode ends).
+ * of scg_bg_step with the same flags (SCG_BG_AUTORESET may cross episode ends), for
+ * both variants: BeerGameEnv (variant 1: actions are order increments) and BeerGameEnv2
+ * (variant 2: absolute orders, observations offset by max_stock, rewards including the
+ * capacity penalty, per-env delays drawn in the launch when stochastic_delays is set;
+ * an auto-reset inside a launch advances the episode the draws are keyed by).
  *   actions DEVICE int32 [K][N][L]; obs DEVICE int32 [K][N][L] or NULL;
  *   rewards DEVICE int32 [K][N] or NULL.
+ * What a rollout does not produce, for either variant: no terminal_obs (with auto-reset
+ * the obs row of a terminal week is the reset observation), and no export of the
+ * overflow word to st->error_host at terminal weeks (the device word st->error_flags is
+ * set as by scg_bg_step; read it after the rollout).
+ * Every argument is checked before any HIP call: SCG_ERR_INVALID (null actions,
+ * n_weeks < 0), SCG_ERR_NOT_RESET, and without SCG_BG_AUTORESET SCG_ERR_PAST_HORIZON
+ * when st->week + n_weeks passes max_weeks; st is untouched on failure.
  */
 SCG_API int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks,
                    const int32_t* actions, int32_t* obs, int32_t* rewards, uint32_t flags,

@@ -1,0 +1,224 @@
+"""BeerGame2VecEnv.rollout (scg_bg_rollout on a variant-2 config: bg2_rollout_kernel /
+bg2_rollout_lds_kernel): K weeks in one call against the reference's golden episodes, against a
+twin env stepped week by week, and against the oracle. Every comparison is exact. N = 300 is
+one full 256-lane block and a 44-lane tail."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from golden_io import beergame2_cases, load_beergame2
+from oracle.beergame import BeerGame2Oracle
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+STATE = ("inventory", "backlog", "orders_placed", "inventory_costs", "backlog_costs", "penalty_costs",
+         "episode_return", "final_return", "all_orders_placed", "_ring")
+LIST_DELAYS = [2, 0, 3, 1, 1, 4, 2, 0, 5, 1, 2, 3]  # delay 0, colliding arrival weeks, arrivals past week 12
+
+
+def _i32(a):
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int32, device=DEV)
+
+
+def _actions(seed, N, K, L, lo=0, hi=29, env_offset=0):
+    """Device-drawn actions [K, N, L] in lo..hi, a function of the global env id."""
+    from gym_supplychain_amd import _native as nat
+    out = torch.empty((K, N, L), dtype=torch.int32, device=DEV)
+    nat.check(nat.lib.scg_uniform_ints(seed, env_offset, N, K, L, 11, lo, hi, out.data_ptr(),
+                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def _env(n, **kw):
+    from gym_supplychain_amd import BeerGame2VecEnv
+    kw.setdefault("track_history", True)
+    return BeerGame2VecEnv(n, device=DEV, **kw)
+
+
+def _steps(env, acts):
+    obs, rew = [], []
+    for k in range(acts.shape[0]):
+        o, r, _, _ = env.step(acts[k])
+        obs.append(o.clone())
+        rew.append(r.clone())
+    return torch.stack(obs), torch.stack(rew)
+
+
+def _assert_same_state(a, b):
+    for t in STATE:
+        assert torch.equal(getattr(a, t), getattr(b, t)), t
+    assert (a.week, a.episode) == (b.week, b.episode)
+
+
+def _assert_rollout_equals_steps(n, K, pre_steps=0, **kw):
+    """A twin pair from reset: one env steps K weeks, the other steps `pre_steps` weeks and rolls
+    out the rest in one call; every obs and reward and the whole state afterwards are equal."""
+    stepped, rolled = _env(n, **kw), _env(n, **kw)
+    acts = _actions(kw.get("seed", 0), n, K, stepped.levels)
+    stepped.reset()
+    rolled.reset()
+    want_obs, want_rew = _steps(stepped, acts)
+    if pre_steps:
+        _steps(rolled, acts[:pre_steps])
+    obs, rew = rolled.rollout(acts[pre_steps:])
+    assert obs.shape == (K - pre_steps, n, stepped.levels) and rew.shape == (K - pre_steps, n)
+    assert torch.equal(obs, want_obs[pre_steps:])
+    assert torch.equal(rew, want_rew[pre_steps:])
+    _assert_same_state(stepped, rolled)
+    stepped.check_errors()
+    rolled.check_errors()
+    return rolled
+
+
+# ---- 1. the reference's golden cases through one call ------------------------------------------
+@pytest.mark.parametrize("name", beergame2_cases())
+def test_rollout_matches_reference(name):
+    g = load_beergame2(name)
+    T, N, L = g["actions"].shape
+    kw = dict(g["kwargs"])
+    for k in ("customer_demand", "shipment_delays"):
+        if isinstance(kw.get(k), list) and len(kw[k]) == 2:
+            kw[k] = tuple(kw[k])
+    env = _env(N, seed=int(g["seed"]), auto_reset=False, **kw)
+    for _ in range(int(g["episode"]) + 1):
+        env.reset()
+    acts = _i32(g["actions"])
+    obs, rew = env.rollout(acts)
+    assert np.array_equal(obs.cpu().numpy(), g["ref_obs"])
+    assert np.array_equal(rew.cpu().numpy(), g["ref_reward"])
+    assert np.array_equal(env.inventory.cpu().numpy(), g["ref_inventory"][T - 1])
+    assert np.array_equal(env.backlog.cpu().numpy(), g["ref_backlog"][T - 1])
+    assert np.array_equal(env.orders_placed.cpu().numpy(), g["ref_orders_placed"][T - 1])
+    for k in ("inventory_costs", "backlog_costs", "penalty_costs"):
+        assert np.array_equal(getattr(env, k).cpu().numpy().astype(np.float64), g["ref_" + k]), k
+    assert np.array_equal(env.all_orders_placed[:, :, 1:].cpu().numpy(), g["ref_orders_placed"].transpose(1, 2, 0))
+    assert env.week == T
+    env.check_errors()
+    with pytest.raises(IndexError):
+        env.rollout(acts[:1])
+
+
+# ---- 2. rollout == steps across episode ends, stochastic draws, LDS ring ------------------------
+def test_rollout_equals_steps_across_episode_ends():
+    env = _assert_rollout_equals_steps(300, 3 * 12 + 5, weeks=12, customer_demand=(0, 16), shipment_delays=(0, 5),
+                                       seed=5)
+    assert env.ring_slots == 5 and (env.week, env.episode) == (5, 3)
+
+
+# ---- 3. the LDS / HBM ring switch -----------------------------------------------------------------
+@pytest.mark.parametrize("levels,delays,slots", [(4, (0, 16), 16), (4, (0, 17), 17), (6, (3, 40), 40)])
+def test_rollout_ring_switch(levels, delays, slots):
+    """R * L * 256 * 4 bytes: 64 KiB exactly (the LDS kernel), one slot more and a wide ring
+    at L = 6 (the HBM kernel)."""
+    env = _assert_rollout_equals_steps(300, 45, weeks=20, levels=levels, initial_inventory=[12] * levels,
+                                       customer_demand=(0, 16), shipment_delays=delays, seed=5)
+    assert env.ring_slots == slots
+
+
+# ---- 4. launch boundaries -------------------------------------------------------------------------
+def test_rollout_launch_boundaries():
+    """Seven steps, then one rollout of 293 weeks: three launches of at most 128 weeks whose
+    boundaries fall mid-episode, across six auto-resets of 50-week episodes."""
+    env = _assert_rollout_equals_steps(300, 300, pre_steps=7, weeks=50, customer_demand=(2, 12),
+                                       shipment_delays=(0, 9), seed=5)
+    assert (env.week, env.episode) == (0, 6)
+
+
+# ---- 5. delay lists ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("levels", [1, 6, 16])
+def test_rollout_delay_list(levels):
+    _assert_rollout_equals_steps(260, 2 * 12 + 3, weeks=12, levels=levels,
+                                 initial_inventory=[12, 8, 4, 9, 1, 15, 7, 3, 11, 6, 2, 14, 5, 10, 13, 0][:levels],
+                                 customer_demand=[3, 9, 0, 5, 7, 2, 8, 4, 6, 1, 10, 5], shipment_delays=LIST_DELAYS,
+                                 seed=5)
+
+
+# ---- 6. against the oracle, into a second episode ---------------------------------------------------
+def test_rollout_matches_oracle_into_second_episode():
+    from oracle.gen_golden_bg2 import STREAM_BG2_DELAY, STREAM_BG2_DEMAND, uniform_table
+    N, T, L, seed = 70, 10, 4, 9
+    env = _env(N, weeks=T, customer_demand=(0, 16), shipment_delays=(0, 5), seed=seed)
+    acts = np.random.RandomState(6).randint(0, 30, size=(2 * T, N, L))
+    reset_obs = env.reset().cpu().numpy().copy()
+    obs, rew = env.rollout(_i32(acts))
+    obs, rew = obs.cpu().numpy(), rew.cpu().numpy()
+    for ep in range(2):
+        demand = uniform_table(seed, N, ep, T, 0, 16, STREAM_BG2_DEMAND)
+        delays = uniform_table(seed, N, ep, T, 0, 5, STREAM_BG2_DELAY)
+        sums = np.zeros(N, dtype=np.int64)
+        for n in range(N):
+            o = BeerGame2Oracle(weeks=T, customer_demand=demand[n], shipment_delays=delays[n].tolist())
+            assert np.array_equal(o.reset(), reset_obs[n] if ep == 0 else obs[T - 1, n]), (ep, n)
+            for w in range(T):
+                want_obs, want_rew, done, _ = o.step(acts[ep * T + w, n])
+                k = ep * T + w
+                if not done:  # the terminal week's obs row is the next episode's reset observation
+                    assert np.array_equal(obs[k, n], want_obs), (ep, n, w)
+                assert rew[k, n] == want_rew, (ep, n, w)
+                sums[n] += want_rew
+            assert done
+        if ep == 1:
+            assert np.array_equal(obs[2 * T - 1], reset_obs)
+            assert np.array_equal(env.final_return.cpu().numpy(), sums)
+    assert (env.week, env.episode) == (0, 2)
+    assert not env.episode_return.any()
+    env.check_errors()
+
+
+# ---- 7. sharding --------------------------------------------------------------------------------------
+def test_rollout_sharding_is_invariant():
+    N, K = 512, 15
+    kw = dict(weeks=12, customer_demand=(0, 16), shipment_delays=(0, 5), seed=5)
+    acts = _actions(5, N, K, 4)
+    whole = _env(N, **kw)
+    parts = [_env(N // 2, env_offset=o, **kw) for o in (0, N // 2)]
+    whole.reset()
+    obs, rew = whole.rollout(acts)
+    got = []
+    for p, sl in zip(parts, (slice(0, N // 2), slice(N // 2, N))):
+        p.reset()
+        got.append(p.rollout(acts[:, sl]))
+    assert torch.equal(obs, torch.cat([g[0] for g in got], dim=1))
+    assert torch.equal(rew, torch.cat([g[1] for g in got], dim=1))
+    for t in STATE:
+        cat_dim = 1 if t == "_ring" else 0
+        assert torch.equal(getattr(whole, t), torch.cat([getattr(p, t) for p in parts], dim=cat_dim)), t
+
+
+# ---- 8. checkpoint ------------------------------------------------------------------------------------
+def test_rollout_resumes_from_a_checkpoint():
+    N = 300
+    kw = dict(weeks=12, customer_demand=(0, 16), shipment_delays=(0, 5), seed=5)
+    acts = _actions(5, N, 37, 4)
+    a = _env(N, **kw)
+    a.reset()
+    a.rollout(acts[:17])
+    state = a.state_dict()
+    b = _env(N, **kw)
+    b.load_state_dict(state)
+    assert (b.week, b.episode) == (5, 1)
+    obs_a, rew_a = a.rollout(acts[17:])
+    obs_b, rew_b = b.rollout(acts[17:])
+    assert torch.equal(obs_a, obs_b) and torch.equal(rew_a, rew_b)
+    _assert_same_state(a, b)
+
+
+# ---- 9. the sticky overflow flag ----------------------------------------------------------------------
+def test_rollout_sets_the_overflow_flag_as_steps_do():
+    N, L = 8, 4
+    big = torch.full((4, N, L), 2 ** 30, dtype=torch.int32, device=DEV)
+    stepped, rolled = _env(N, auto_reset=False), _env(N, auto_reset=False)
+    stepped.reset()
+    rolled.reset()
+    _steps(stepped, big)
+    rolled.rollout(big)
+    with pytest.raises(OverflowError):
+        stepped.check_errors()
+    with pytest.raises(OverflowError):
+        rolled.check_errors()
+    fine = _env(N, auto_reset=False)
+    fine.reset()
+    fine.rollout(_actions(1, N, 4, L))
+    fine.check_errors()

@@ -1,0 +1,108 @@
+"""BeerGameEnv2: a loop of step() calls against one rollout() per episode, A/B in one process.
+
+    python tools/bg2_rollout_ab.py [--envs 65536] [--episodes 200] [--pairs 5]
+
+BeerGame2VecEnv at L = 4, 35 weeks, customer_demand=(0, 16), shipment_delays=(0, 5) (random
+demand and per-env random delays, ledgers and returns kept, auto-reset). A sample is the wall
+clock of `--episodes` whole episodes between two device synchronisations: as 35 step() calls
+per episode (bg2_step_kernel, one launch per week) or as one rollout() of 35 weeks per episode
+(bg2_rollout_lds_kernel). The two alternate, `--pairs` times, after one untimed sample of each;
+before that one episode of both is compared bit for bit. Prints one JSON line per sample and a
+summary line: medians and max - min of the time per env-step, and whether the rollout's median
+lies below the step loop's by more than the step loop's own max - min (DESIGN §6.1's rule).
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.environ.get("SCG_PKG_ROOT") or os.path.join(REPO, "gym-supplychain_amd"))
+sys.path.insert(0, REPO)
+
+LEVELS, WEEKS, SEED = 4, 35, 0x5EED0000
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--episodes", type=int, default=200)
+    ap.add_argument("--pairs", type=int, default=5)
+    a = ap.parse_args()
+
+    import torch
+
+    from gym_supplychain_amd import BeerGame2VecEnv
+    from gym_supplychain_amd import _native as nat
+    dev = torch.device("cuda", 0)
+    N, L, T = a.envs, LEVELS, WEEKS
+
+    def make():
+        env = BeerGame2VecEnv(N, weeks=T, levels=L, customer_demand=(0, 16), shipment_delays=(0, 5), seed=SEED,
+                              device=dev)
+        env.reset()
+        return env
+
+    stepped, rolled = make(), make()
+    acts = torch.empty((T, N, L), dtype=torch.int32, device=dev)
+    nat.check(nat.lib.scg_uniform_ints(SEED, 0, N, T, L, 0, 0, 29, acts.data_ptr(),
+                                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    week = list(acts.unbind(0))
+    obs = torch.empty((T, N, L), dtype=torch.int32, device=dev)
+    rew = torch.empty((T, N), dtype=torch.int32, device=dev)
+
+    # the two paths compute the same episode (at the timed size)
+    rolled.rollout(acts, obs, rew)
+    for w in range(T):
+        o, r, _, _ = stepped.step(week[w])
+        if not (torch.equal(o, obs[w]) and torch.equal(r, rew[w])):
+            raise SystemExit(f"rollout and step loop differ at week {w + 1}")
+    for t in ("inventory", "backlog", "orders_placed", "final_return", "_ring"):
+        if not torch.equal(getattr(stepped, t), getattr(rolled, t)):
+            raise SystemExit(f"rollout and step loop differ in {t}")
+
+    def step_loop():
+        for _ in range(a.episodes):
+            for w in range(T):
+                stepped.step(week[w])
+
+    def rollouts():
+        for _ in range(a.episodes):
+            rolled.rollout(acts, obs, rew)
+
+    def sample(fn):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize(dev)
+        return (time.perf_counter() - t0) / (a.episodes * T * N) * 1e9  # ns per env-step
+
+    sample(step_loop)
+    sample(rollouts)
+    got = {"step_loop": [], "rollout": []}
+    for pair in range(a.pairs):
+        for name, fn in (("step_loop", step_loop), ("rollout", rollouts)):
+            ns = sample(fn)
+            got[name].append(ns)
+            print(json.dumps({"pair": pair, "path": name, "ns_per_env_step": ns,
+                              "us_per_episode": ns * T * N / 1e3}), flush=True)
+    stepped.check_errors()
+    rolled.check_errors()
+    med = {k: statistics.median(v) for k, v in got.items()}
+    spread = {k: max(v) - min(v) for k, v in got.items()}
+    print(json.dumps({"n_envs": N, "levels": L, "weeks": T, "episodes_per_sample": a.episodes, "pairs": a.pairs,
+                      "step_loop_median_ns_per_env_step": med["step_loop"],
+                      "step_loop_max_minus_min": spread["step_loop"],
+                      "rollout_median_ns_per_env_step": med["rollout"], "rollout_max_minus_min": spread["rollout"],
+                      "step_loop_median_us_per_week": med["step_loop"] * N / 1e3,
+                      "rollout_median_us_per_week": med["rollout"] * N / 1e3,
+                      "speedup": med["step_loop"] / med["rollout"],
+                      "rollout_below_by_more_than_step_spread":
+                          med["step_loop"] - med["rollout"] > spread["step_loop"]}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
