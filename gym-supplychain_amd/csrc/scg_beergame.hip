@@ -635,6 +635,56 @@ int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, 
   return SCG_OK;
 }
 
+int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_policy* policy,
+                          int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum, uint32_t flags,
+                          void* stream) {
+  if (int rc = check_state(cfg, st)) return rc;
+  if (!policy || !policy->params) return fail(SCG_ERR_INVALID, "policy rollout needs a policy with params");
+  if (policy->kind != SCG_BG_POLICY_LINEAR) return fail(SCG_ERR_INVALID, "unknown policy kind %d", policy->kind);
+  if (!policy_valid(policy->kind, policy->shift, policy->act_lo, policy->act_hi))
+    return fail(SCG_ERR_INVALID, "policy needs shift in 0..%d and act_lo <= act_hi (got shift=%d, clamp %d..%d)",
+                kPolicyMaxShift, policy->shift, policy->act_lo, policy->act_hi);
+  if (cfg->levels > SCG_BG_POLICY_MAX_LEVELS)
+    return fail(SCG_ERR_INVALID, "policy rollout: levels=%d above %d", cfg->levels, SCG_BG_POLICY_MAX_LEVELS);
+  if (n_weeks < 0) return fail(SCG_ERR_INVALID, "policy rollout needs n_weeks >= 0");
+  if (int rc = check_step(cfg, st)) return rc;
+  if (!(flags & SCG_BG_AUTORESET) && st->week + static_cast<int64_t>(n_weeks) > cfg->max_weeks)
+    return fail(SCG_ERR_PAST_HORIZON, "rollout of %d weeks from week %d passes the terminal week %d", n_weeks,
+                st->week, cfg->max_weeks);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_weeks == 0) {  // no launch: the sum of no rewards
+    if (reward_sum && hipMemsetAsync(reward_sum, 0, static_cast<size_t>(st->n_envs) * sizeof(int64_t), s) != hipSuccess)
+      return fail(SCG_ERR_HIP, "hipMemsetAsync(reward_sum) failed");
+    return SCG_OK;
+  }
+  const int64_t stride = st->n_envs * cfg->levels;
+  int32_t done_k = 0;
+  while (done_k < n_weeks) {  // launches of up to SCG_BG_ROLLOUT_MAX weeks, as scg_bg_rollout cuts them
+    RolloutWeeks weeks;
+    int32_t K = 0;
+    scg_bg_state probe = *st;
+    const BgArgs a = make_args(cfg, st);
+    while (K < SCG_BG_ROLLOUT_MAX && done_k + K < n_weeks) {
+      weeks.wk[K] = week_info(cfg, probe.week + 1, flags);
+      advance_week(&probe, weeks.wk[K]);
+      ++K;
+    }
+    PolicyArgs pa;
+    pa.params = policy->params;
+    pa.acts_out = actions_out ? actions_out + done_k * stride : nullptr;
+    pa.obs_out = obs ? obs + done_k * stride : nullptr;
+    pa.rew_out = rewards ? rewards + done_k * st->n_envs : nullptr;
+    pa.reward_sum = reward_sum;
+    pa.clamp = PolicyClamp{policy->shift, policy->act_lo, policy->act_hi};
+    pa.first = done_k == 0;
+    if (int rc = bg_launch_policy_rollout(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, pa)) return rc;
+    st->week = probe.week;
+    st->episode = probe.episode;
+    done_k += K;
+  }
+  return SCG_OK;
+}
+
 int scg_bg_poisson_demand(const scg_bg_config* cfg, const scg_bg_state* st, uint32_t episode, int32_t* out,
                           void* stream) {
   if (int rc = check_state(cfg, st)) return rc;

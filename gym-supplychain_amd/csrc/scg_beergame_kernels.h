@@ -2,7 +2,8 @@
 // instantiation units scg_bg_levels_*.hip): the reset / step / slab step / BeerGameEnv2 /
 // rollout kernels, templated on the level count L, and one launcher per kernel family and
 // L. scg_beergame.hip dispatches on L at run time; the launchers are instantiated in four
-// units (levels 1-4, 5-8, 9-12, 13-16) that compile in parallel.
+// units (levels 1-4, 5-8, 9-12, 13-16) that compile in parallel. The closed-loop policy
+// rollout kernels (levels 1-8) are instantiated, with their launcher, in scg_bg_policy.hip.
 //
 // BeerGame hot path for gfx950: reset / step / rollout kernels + their C-ABI launchers.
 //
@@ -31,6 +32,7 @@
 #include <type_traits>
 
 #include "scg_bg_plan.h"
+#include "scg_bg_policy.h"
 #include "scg_common.h"
 #include "scg_mailbox.h"
 #include "scg_const.h"
@@ -1245,6 +1247,263 @@ __global__ __launch_bounds__(kBlock) void bg2_rollout_lds_kernel(const BgArgs a,
     hbm.store(s, v);
   }
 }
+
+// ---- closed-loop rollouts with a per-env linear policy (scg_bg_rollout_policy) ------------
+// The rollout kernels above with the action row computed instead of read: each lane loads its
+// L*(L+1) parameter words once per launch (word q of a wave's 64 envs is one coalesced
+// 256-byte row) and keeps them in registers beside the state; each week it forms the
+// observation the env last produced from its inventory and backlog registers, the L int64
+// dot products, the shift and the clamp (scg_bg_policy.h), and then runs the week as the
+// open-loop bodies do. No action rows are requested, so the weeks are not grouped. Every
+// output is optional: with none, and the ring in LDS, a FIXED, POISSON or UNIFORM week touches
+// no HBM (history rows excepted). The sum of the launch's rewards is one int64 per lane.
+// The bodies are copies of rollout_body / rollout2_body on purpose: those keep their
+// generated code (DESIGN §6.1 on what a shared body cost the slab kernel's schedule).
+struct PolicyArgs {
+  const int32_t* params;  // [L*(L+1)][N]
+  int32_t* acts_out;      // [K][N][L] of this launch, or null
+  int32_t* obs_out;       // [K][N][L] or null
+  int32_t* rew_out;       // [K][N] or null
+  int64_t* reward_sum;    // [N] or null
+  PolicyClamp clamp;
+  int32_t first;          // the first launch of a call stores reward_sum, later ones add to it
+};
+
+template <int L, class Ring>
+__device__ __forceinline__ void policy_rollout_body(const BgArgs& a, int64_t n, int32_t K, const RolloutWeeks& weeks,
+                                                    const PolicyArgs& pa, const Ring& ring) {
+  const int64_t row = n * L;
+  const int64_t stride = a.n * L;
+  int32_t par[L * (L + 1)];
+  policy_load<L>(pa.params, a.n, n, par);
+  int32_t inv[L], bk[L], op[L], iacc[L], bacc[L];
+  load_row<L>(a.inv + row, inv);
+  load_row<L>(a.bk + row, bk);
+  load_row<L>(a.op + row, op);
+  zero_row<L>(iacc);
+  zero_row<L>(bacc);
+  if (a.inv_acc) load_row<L>(a.inv_acc + row, iacc);
+  if (a.bk_acc) load_row<L>(a.bk_acc + row, bacc);
+  int64_t ret = a.ep_ret ? a.ep_ret[n] : 0;
+  int64_t sum = 0;
+  uint32_t episode = a.episode;
+  bool ovf = false;
+  for (int32_t k = 0; k < K; ++k) {
+    const WeekInfo wk = weeks.wk[k];
+    int32_t o[L], act[L], due[L], obs[L], ship[L], cur[L];
+    policy_obs<L>(inv, bk, 0, o);
+    policy_act<L>(par, o, pa.clamp, act);
+    zero_row<L>(due);
+    if (wk.read_slot >= 0) ring.load(wk.read_slot, due);
+    int32_t demand;
+    if (a.demand_mode == SCG_DEMAND_FIXED)
+      demand = wk.demand_fixed;
+    else
+      demand = week_demand(a, n, wk.week, episode);
+    zero_row<L>(cur);
+    if (wk.mode == MODE_ADD) ring.load(wk.write_slot, cur);
+    const int32_t reward = week_update<L>(a.h, a.b, a.guard, demand, wk.mode == MODE_DIRECT, due, inv, bk, op, act, ship,
+                                          obs, cur, iacc, bacc, ovf);
+    if (wk.mode == MODE_STORE) {
+      ring.store(wk.write_slot, ship);
+    } else if (wk.mode == MODE_ADD) {
+      ring.store(wk.write_slot, cur);
+    }
+    if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
+    ret += reward;
+    sum += reward;
+    if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
+    if (wk.flags & WEEK_AUTORESET) {  // auto-reset in registers (:140-156)
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        inv[l] = a.init_inv[l];
+        bk[l] = 0;
+        op[l] = a.orders_value;
+        iacc[l] = bacc[l] = 0;
+        obs[l] = inv[l];
+      }
+      int32_t init[L];
+#pragma unroll
+      for (int l = 0; l < L; ++l) init[l] = a.ship_value;
+      for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, init);
+      if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
+      ret = 0;
+      ++episode;
+    }
+    if (pa.acts_out) store_row<L>(pa.acts_out + k * stride + row, act);
+    if (pa.obs_out) store_row<L>(pa.obs_out + k * stride + row, obs);
+    if (pa.rew_out) pa.rew_out[k * a.n + n] = reward;
+  }
+  store_row<L>(a.inv + row, inv);
+  store_row<L>(a.bk + row, bk);
+  store_row<L>(a.op + row, op);
+  if (a.inv_acc) store_row<L>(a.inv_acc + row, iacc);
+  if (a.bk_acc) store_row<L>(a.bk_acc + row, bacc);
+  if (a.ep_ret) a.ep_ret[n] = ret;
+  if (pa.reward_sum) pa.reward_sum[n] = pa.first ? sum : pa.reward_sum[n] + sum;
+  note_overflow(a.err, ovf);
+}
+
+// BeerGameEnv2: rollout2_body's week (per-lane stochastic-delay slots, the in-register reset)
+// behind the same policy; the observation carries max_stock.
+template <int L, class Ring>
+__device__ __forceinline__ void policy_rollout2_body(const BgArgs& a, int64_t n, int32_t K, const RolloutWeeks& weeks,
+                                                     const PolicyArgs& pa, const Ring& ring) {
+  const int64_t row = n * L;
+  const int64_t stride = a.n * L;
+  int32_t par[L * (L + 1)];
+  policy_load<L>(pa.params, a.n, n, par);
+  int32_t inv[L], bk[L], op[L], iacc[L], bacc[L], pacc[L];
+  load_row<L>(a.inv + row, inv);
+  load_row<L>(a.bk + row, bk);
+  load_row<L>(a.op + row, op);
+  zero_row<L>(iacc);
+  zero_row<L>(bacc);
+  zero_row<L>(pacc);
+  if (a.inv_acc) load_row<L>(a.inv_acc + row, iacc);
+  if (a.bk_acc) load_row<L>(a.bk_acc + row, bacc);
+  if (a.pen_acc) load_row<L>(a.pen_acc + row, pacc);
+  int64_t ret = a.ep_ret ? a.ep_ret[n] : 0;
+  int64_t sum = 0;
+  uint32_t episode = a.episode;
+  bool ovf = false;
+  for (int32_t k = 0; k < K; ++k) {
+    const WeekInfo wk = weeks.wk[k];
+    const bool autoreset = wk.flags & WEEK_AUTORESET;
+    int32_t read_slot = wk.read_slot, write_slot = wk.write_slot, mode = wk.mode;
+    if (a.stochastic_delays) {
+      const uint32_t w = scg::philox_word(a.key0, a.key1, static_cast<uint32_t>(a.env_offset + n), episode,
+                                          static_cast<uint32_t>(wk.week - 1), SCG_STREAM_BG2_DELAY);
+      const int32_t d = a.delay_lo + static_cast<int32_t>((static_cast<uint64_t>(w) * static_cast<uint32_t>(a.delay_hi - a.delay_lo)) >> 32);
+      read_slot = wk.week % a.ring_slots;
+      write_slot = (wk.week + d) % a.ring_slots;
+      mode = d == 0 ? MODE_DIRECT : (wk.week + d > a.max_weeks ? MODE_DROP : MODE_ADD);
+    }
+    int32_t o[L], act[L], due[L], obs[L], ship[L], cur[L];
+    policy_obs<L>(inv, bk, a.max_stock, o);
+    policy_act<L>(par, o, pa.clamp, act);
+    zero_row<L>(due);
+    zero_row<L>(cur);
+    if (read_slot >= 0) ring.load(read_slot, due);
+    if (mode == MODE_ADD) ring.load(write_slot, cur);
+    if (autoreset) {  // the step kernel starts an auto-reset week's ledgers from zero (they end zeroed)
+      zero_row<L>(iacc);
+      zero_row<L>(bacc);
+      zero_row<L>(pacc);
+    }
+    const int32_t demand = a.demand_mode == SCG_DEMAND_FIXED ? wk.demand_fixed : week_demand(a, n, wk.week, episode);
+    const int32_t reward = week2_update<L>(a, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship, obs, iacc, bacc,
+                                           pacc, ovf);
+    if (a.stochastic_delays) {  // consumed: the slot is reused R weeks on
+      zero_row<L>(due);
+      ring.store(read_slot, due);
+    }
+    if (mode == MODE_STORE) {
+      ring.store(write_slot, ship);
+    } else if (mode == MODE_ADD) {
+      add_ship<L>(cur, ship, ovf);
+      ring.store(write_slot, cur);
+    }
+    if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
+    ret += reward;
+    sum += reward;
+    if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
+    if (autoreset) {  // reset_env in registers and on the ring view
+      int32_t v[L];
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        inv[l] = a.init_inv[l];
+        bk[l] = 0;
+        op[l] = a.orders_value;
+        iacc[l] = bacc[l] = pacc[l] = 0;
+        obs[l] = inv[l] + a.max_stock;
+        v[l] = 0;
+      }
+      if (a.stochastic_delays)
+        for (int s = 0; s < a.ring_slots; ++s) ring.store(s, v);
+#pragma unroll
+      for (int l = 0; l < L; ++l) v[l] = a.ship_value;
+      for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, v);
+      if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
+      ret = 0;
+      ++episode;
+    }
+    if (pa.acts_out) store_row<L>(pa.acts_out + k * stride + row, act);
+    if (pa.obs_out) store_row<L>(pa.obs_out + k * stride + row, obs);
+    if (pa.rew_out) pa.rew_out[k * a.n + n] = reward;
+  }
+  store_row<L>(a.inv + row, inv);
+  store_row<L>(a.bk + row, bk);
+  store_row<L>(a.op + row, op);
+  if (a.inv_acc) store_row<L>(a.inv_acc + row, iacc);
+  if (a.bk_acc) store_row<L>(a.bk_acc + row, bacc);
+  if (a.pen_acc) store_row<L>(a.pen_acc + row, pacc);
+  if (a.ep_ret) a.ep_ret[n] = ret;
+  if (pa.reward_sum) pa.reward_sum[n] = pa.first ? sum : pa.reward_sum[n] + sum;
+  note_overflow(a.err, ovf);
+}
+
+// The ring of one lane between HBM and its LDS column, around a launch.
+template <int L>
+__device__ __forceinline__ void policy_ring_copy(const RingHbm<L>& hbm, const RingLds<L>& lds, int32_t slots, bool in) {
+  for (int s = 0; s < slots; ++s) {
+    int32_t v[L];
+    if (in) {
+      hbm.load(s, v);
+      lds.store(s, v);
+    } else {
+      lds.load(s, v);
+      hbm.store(s, v);
+    }
+  }
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void bg_policy_rollout_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
+                                                                   const PolicyArgs pa) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (n >= a.n) return;
+  policy_rollout_body<L>(a, n, K, weeks, pa, RingHbm<L>{a.ring, a.n * L, n * L});
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void bg_policy_rollout_lds_kernel(const BgArgs a, int32_t K,
+                                                                       const RolloutWeeks weeks, const PolicyArgs pa) {
+  extern __shared__ int32_t lds_ring[];
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (n >= a.n) return;  // lanes only touch their own LDS column: no block barrier needed
+  const RingHbm<L> hbm{a.ring, a.n * L, n * L};
+  const RingLds<L> lds{lds_ring + threadIdx.x};
+  policy_ring_copy<L>(hbm, lds, a.ring_slots, true);
+  policy_rollout_body<L>(a, n, K, weeks, pa, lds);
+  policy_ring_copy<L>(hbm, lds, a.ring_slots, false);
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void bg2_policy_rollout_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
+                                                                    const PolicyArgs pa) {
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (n >= a.n) return;
+  policy_rollout2_body<L>(a, n, K, weeks, pa, RingHbm<L>{a.ring, a.n * L, n * L});
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void bg2_policy_rollout_lds_kernel(const BgArgs a, int32_t K,
+                                                                        const RolloutWeeks weeks, const PolicyArgs pa) {
+  extern __shared__ int32_t lds_ring[];
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (n >= a.n) return;  // lanes only touch their own LDS column: no block barrier needed
+  const RingHbm<L> hbm{a.ring, a.n * L, n * L};
+  const RingLds<L> lds{lds_ring + threadIdx.x};
+  policy_ring_copy<L>(hbm, lds, a.ring_slots, true);
+  policy_rollout2_body<L>(a, n, K, weeks, pa, lds);
+  policy_ring_copy<L>(hbm, lds, a.ring_slots, false);
+}
+
+// The policy rollout of `variant` at L levels (1..SCG_BG_POLICY_MAX_LEVELS), by the ring rule
+// of bg_launch_rollout; defined in scg_bg_policy.hip, the unit that instantiates these kernels.
+int bg_launch_policy_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
+                             const RolloutWeeks& weeks, const PolicyArgs& pa);
 
 // hipModuleLaunchKernel with the kernel's function handle resolved once per instantiation,
 // skipping the host-stub lookup of hipLaunchKernel on every step: ≈0.5 µs less host time

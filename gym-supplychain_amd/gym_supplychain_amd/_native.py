@@ -43,6 +43,9 @@ BG_MAX_WEEKS = 4096
 BG_MAX_DELAY = 4096
 POISSON_MAX = 256
 BG_ROLLOUT_MAX = 128
+BG_POLICY_LINEAR = 1  # scg_bg_policy.kind
+BG_POLICY_MAX_LEVELS = 8
+BG_POLICY_MAX_SHIFT = 30
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -110,6 +113,12 @@ BG_STEP_CONSTS_BYTES = 512  # SCG_BG_STEP_CONSTS_BYTES: the slab step kernel's c
 
 BG_SERVER_SLOTS = 15
 BG_SERVER_ARGS_BYTES = 512
+
+
+class BgPolicy(ctypes.Structure):
+    """scg_bg_policy (include/scgpu.h): the per-env linear policy of scg_bg_rollout_policy."""
+    _fields_ = [("kind", ctypes.c_int32), ("shift", ctypes.c_int32), ("act_lo", ctypes.c_int32),
+                ("act_hi", ctypes.c_int32), ("params", ctypes.c_void_p)]
 
 
 class BgServerLine(ctypes.Structure):
@@ -258,6 +267,9 @@ SIGNATURES = {
     "scg_bg_rollout": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_int32,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                       ctypes.c_void_p]),
+    "scg_bg_rollout_policy": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_int32,
+                                             ctypes.POINTER(BgPolicy), ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "scg_bg_poisson_demand": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState),
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_struct_sizes": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)] * 3),

@@ -102,6 +102,24 @@ class BeerGameConfig:
         self.initial_orders_value = _int32("initial_orders_value", info.get("initial_orders_value", STD_ORDERS_VALUE))
 
 
+class PackedPolicy:
+    """Per-env linear policy parameters as scg_bg_rollout_policy reads them
+    (BeerGameVecEnv.pack_policy): `params` int32 [L*(L+1), N] on the env's device."""
+    __slots__ = ("params", "n_envs", "levels")
+
+    def __init__(self, params, n_envs, levels):
+        self.params, self.n_envs, self.levels = params, n_envs, levels
+
+
+class PolicyRollout:
+    """What BeerGameVecEnv.rollout_policy returns: `reward_sum` int64 [N], and `actions`
+    [K, N, L], `obs` [K, N, L], `rewards` [K, N] (int32) where requested, else None."""
+    __slots__ = ("reward_sum", "actions", "obs", "rewards")
+
+    def __init__(self, reward_sum, actions=None, obs=None, rewards=None):
+        self.reward_sum, self.actions, self.obs, self.rewards = reward_sum, actions, obs, rewards
+
+
 class BeerGameVecEnv:
     """N lock-step Beer Game envs on one GPU, state resident in HBM.
 
@@ -442,6 +460,89 @@ class BeerGameVecEnv:
         nat.check(nat.lib.scg_bg_rollout(self._cfg_ref, self._st_ref, K, actions.data_ptr(), obs_out.data_ptr(),
                                          rewards_out.data_ptr(), self._flags, self._stream()))
         return obs_out, rewards_out
+
+    # closed-loop rollout with a per-env linear policy (scg_bg_rollout_policy) ------------
+    def _policy_clip(self):
+        """The clamp of rollout_policy(clip=None): the whole int32 range (order increments)."""
+        return _I32
+
+    def _exact_int32(self, name, x, shapes):
+        """x as an int32 tensor on this env's device, of one of `shapes`; ValueError when the
+        shape is another or a value does not survive the cast."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x))
+        if tuple(x.shape) not in shapes:
+            raise ValueError(f"{name} must have shape {' or '.join(str(list(s)) for s in shapes)}, "
+                             f"got {list(x.shape)}")
+        if x.dtype == torch.bool or x.dtype.is_complex:
+            raise ValueError(f"{name} must be integers, got {x.dtype}")
+        x = x.to(self.device)
+        if x.dtype != torch.int32:
+            y = x.to(torch.int32)
+            if x.numel() and not bool((y.to(x.dtype) == x).all()):
+                raise ValueError(f"{name} ({x.dtype}) holds values that are not int32 integers")
+            x = y
+        return x
+
+    def pack_policy(self, weights, bias):
+        """Per-env linear policy parameters in the layout scg_bg_rollout_policy reads: int32
+        [L*(L+1), N] on this env's device, word l*(L+1)+j of an env being weights[l][j] for
+        j < L and bias[l] for j == L. weights is [N, L, L] or [L, L], bias [N, L] or [L]
+        (shared forms are broadcast). Pass the result to rollout_policy() to pack once for
+        many calls."""
+        N, L = self.n_envs, self.levels
+        if L > nat.BG_POLICY_MAX_LEVELS:
+            raise ValueError(f"rollout_policy supports up to {nat.BG_POLICY_MAX_LEVELS} levels, this env has {L}")
+        w = self._exact_int32("weights", weights, ((N, L, L), (L, L))).expand(N, L, L)
+        b = self._exact_int32("bias", bias, ((N, L), (L,))).expand(N, L)
+        words = torch.cat([w, b.unsqueeze(2)], dim=2).reshape(N, L * (L + 1))
+        return PackedPolicy(words.t().contiguous(), N, L)
+
+    def rollout_policy(self, weights, bias=None, n_weeks=None, shift=0, clip=None, return_actions=False,
+                       return_obs=False, return_rewards=False):
+        """n_weeks weeks in as few launches as possible with every env's action computed on the
+        device from its own last observation o (what reset() or the previous step returned):
+
+            z = bias + weights @ o      (int64, wrapping)
+            action = clamp(z >> shift, clip)      (arithmetic shift: floor)
+
+        The same results as n_weeks step() calls given those actions. weights / bias as for
+        pack_policy(), or weights a pack_policy() result and bias None. shift in 0..30; clip
+        (lo, hi) with lo <= hi, None for the int32 range (BeerGame2VecEnv: (0, max_order)).
+        Returns a PolicyRollout: reward_sum int64 [N], the sum of the call's rewards per env
+        (across auto-resets), and on request actions [K, N, L], obs [K, N, L], rewards [K, N].
+        With weights = -g * I, bias = g * S and shift = log2 of the scale this is the smoothed
+        order-up-to rule on net stock."""
+        N, L = self.n_envs, self.levels
+        if isinstance(weights, PackedPolicy):
+            if bias is not None:
+                raise ValueError("a packed policy carries its bias")
+            packed = weights
+            if (packed.n_envs, packed.levels) != (N, L) or packed.params.device != self.device:
+                raise ValueError(f"the policy was packed for {packed.n_envs} envs of {packed.levels} levels on "
+                                 f"{packed.params.device}")
+        else:
+            packed = self.pack_policy(weights, bias)
+        if n_weeks is None or isinstance(n_weeks, bool) or not isinstance(n_weeks, (numbers.Integral, np.integer)):
+            raise ValueError("n_weeks must be an integer")
+        if isinstance(shift, bool) or not isinstance(shift, (numbers.Integral, np.integer)) \
+                or not 0 <= shift <= nat.BG_POLICY_MAX_SHIFT:
+            raise ValueError(f"shift must be an integer in 0..{nat.BG_POLICY_MAX_SHIFT}, got {shift!r}")
+        lo, hi = self._policy_clip() if clip is None else clip
+        lo, hi = _int32("clip low", lo), _int32("clip high", hi)
+        if lo > hi:
+            raise ValueError(f"clip=({lo}, {hi}) is empty")
+        K = max(int(n_weeks), 0)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        res = PolicyRollout(torch.empty(N, dtype=torch.int64, device=self.device),
+                            torch.empty((K, N, L), **i32) if return_actions else None,
+                            torch.empty((K, N, L), **i32) if return_obs else None,
+                            torch.empty((K, N), **i32) if return_rewards else None)
+        pol = nat.BgPolicy(nat.BG_POLICY_LINEAR, int(shift), lo, hi, packed.params.data_ptr())
+        nat.check(nat.lib.scg_bg_rollout_policy(self._cfg_ref, self._st_ref, int(n_weeks), ctypes.byref(pol),
+                                                nat.ptr(res.actions), nat.ptr(res.obs), nat.ptr(res.rewards),
+                                                res.reward_sum.data_ptr(), self._flags, self._stream()))
+        return res
 
     def poisson_demand(self, episode=None):
         """The Poisson demand [T, N] the kernels draw for `episode` (default: current)."""
@@ -889,6 +990,10 @@ class BeerGame2VecEnv(BeerGameVecEnv):
         L = cfg.levels
         self.single_observation_space = spaces.Box(0, 2 * cfg.max_stock - 1, (L,), np.int32)   # MultiDiscrete (:28)
         self.single_action_space = spaces.Box(0, cfg.max_order - 1, (L,), np.int32)            # MultiDiscrete (:27)
+
+    def _policy_clip(self):
+        """rollout_policy(clip=None) clamps the absolute orders to (0, max_order)."""
+        return 0, self.max_order
 
 
 class BeerGameEnv2(spaces.Env):

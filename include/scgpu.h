@@ -45,7 +45,8 @@ extern "C" {
  * 8: scg_bg_state ends with step_consts / step_consts_tag: the device block of the slab
  *   step kernel's launch constants (SCG_BG_STEP_CONSTS_BYTES).
  * 9: scg_sc_rollout (K SupplyChain steps per call, SCG_SC_ROLLOUT_MAX, SCG_SC_LAST_OBS) and
- *   the testing hook scg_sc_rollout_chunk. */
+ *   the testing hook scg_sc_rollout_chunk; also scg_bg_rollout_policy (scg_bg_policy: the
+ *   closed-loop BeerGame rollout with a per-env linear policy), an added entry point. */
 #define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
@@ -385,6 +386,45 @@ SCG_API uint32_t scg_bg_server_line_check(const scg_bg_server_line* line);
 SCG_API int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks,
                    const int32_t* actions, int32_t* obs, int32_t* rewards, uint32_t flags,
                    void* stream);
+
+/*
+ * Closed-loop rollout: K weeks per launch as scg_bg_rollout runs them, with each env's
+ * action computed in registers from the observation the env last produced (what
+ * scg_bg_reset or the previous week returned: inventory - backlog, for variant 2 plus
+ * max_stock; after an auto-reset inside the launch, the reset observation) by a per-env
+ * linear policy. For observation o[0..L) and parameters W[L][L], b[L] (int32):
+ *   z_l = b_l + sum_j W[l][j] * o_j         int64, two's-complement wrap
+ *   a_l = min(max(z_l >> shift, act_lo), act_hi)   arithmetic shift (floor), then the clamp
+ * (csrc/scg_bg_policy.h is the one definition, host and device). With W = -g I, b = g S and
+ * shift = log2 of the scale this is the smoothed order-up-to rule on net stock: for variant 1
+ * the action is the increment over the incoming order, for variant 2 the absolute order
+ * (clamp (0, max_order)).
+ * The call equals n_weeks calls of scg_bg_step with the same flags, each with the action row
+ * the formula gives for the previous observation: both variants, every demand mode, delay
+ * lists and stochastic_delays; SCG_BG_AUTORESET may cross episode ends. As for
+ * scg_bg_rollout there is no terminal_obs and no export to st->error_host.
+ *   actions_out DEVICE int32 [K][N][L], the actions taken;  obs DEVICE int32 [K][N][L];
+ *   rewards DEVICE int32 [K][N];  reward_sum DEVICE int64 [N], the sum of this call's K
+ *   rewards per env (across auto-resets and launches; overwritten, not accumulated over
+ *   calls). Each of the four may be NULL; with all four NULL and the ring in LDS a FIXED,
+ *   POISSON or UNIFORM week touches no HBM (history rows excepted, when kept).
+ * Every argument is checked before any HIP call, and st is untouched on failure:
+ * SCG_ERR_INVALID (null policy or params, unknown kind, shift outside 0..30, act_lo > act_hi,
+ * levels > SCG_BG_POLICY_MAX_LEVELS, n_weeks < 0), SCG_ERR_NOT_RESET, and without
+ * SCG_BG_AUTORESET SCG_ERR_PAST_HORIZON.
+ */
+#define SCG_BG_POLICY_LINEAR 1
+#define SCG_BG_POLICY_MAX_LEVELS 8
+typedef struct scg_bg_policy {
+  int32_t kind;            /* SCG_BG_POLICY_LINEAR */
+  int32_t shift;           /* 0..30 */
+  int32_t act_lo, act_hi;
+  const int32_t* params;   /* DEVICE int32 [L*(L+1)][N], env fastest: word l*(L+1)+j is W[l][j] for j < L, b[l] for j == L */
+} scg_bg_policy;
+
+SCG_API int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks,
+                                  const scg_bg_policy* policy, int32_t* actions_out, int32_t* obs,
+                                  int32_t* rewards, int64_t* reward_sum, uint32_t flags, void* stream);
 
 /*
  * Device-side Philox draws for tests and benchmarks (no host round trip):
