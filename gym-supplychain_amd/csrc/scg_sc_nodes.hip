@@ -28,9 +28,11 @@
 // node after node in the reference's order (sc_nodes_serial). Observations and actions go
 // through LDS tiles so HBM sees whole rows; the state pointers stay the batch's base
 // pointers (ScEnv soff/hoff) so they live in SGPRs.
-// The same tile code runs under two more drivers: the rollout kernel (a step loop inside the
-// tile loop, the state in LDS between a launch's steps) and the step server (one resident
-// block serving a drop-in env's steps).
+// The same tile code runs under three more drivers: the rollout kernel (a step loop inside the
+// tile loop, the state in LDS between a launch's steps), the closed-loop rollout kernel (the
+// same, with each step's action tile computed from the previous step's observation tile by a
+// linear policy, scg_sc_policy.h) and the step server (one resident block serving a drop-in
+// env's steps).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -72,6 +74,7 @@ struct ScAcc {  // a marker: a non-null ScEnv::dbg turns the section stamps on
 #include "scg_supplychain_core.h"
 #include "scg_supplychain_args.h"
 #include "scg_supplychain_nodes.h"
+#include "scg_sc_policy.h"
 
 // Diagnostic build only (-DSCG_NODES_STAMPS, tools/nodes_stamps.py): lane 0 of every wave
 // records the shader clock at the phase boundaries (0 start, 5 heaps staged, 6 past the first
@@ -156,6 +159,7 @@ struct NodesLaunchStep {  // the batch kernel: the step fields of the launch arg
   static constexpr bool kKeepsState = false;
   static constexpr bool kStreamOut = true;
   static constexpr bool kObsOptional = false;
+  static constexpr bool kPolicy = false;
   const ScArgs& a;
   __device__ __forceinline__ int t() const { return a.t; }
   __device__ __forceinline__ int flags() const { return a.flags; }
@@ -176,6 +180,7 @@ struct NodesRolloutStep {
   static constexpr bool kKeepsState = true;  // the episode return travels in LDS (ret0)
   static constexpr bool kStreamOut = true;
   static constexpr bool kObsOptional = true;
+  static constexpr bool kPolicy = false;
   int32_t t_, flags_;
   uint32_t episode_;
   int32_t k_;        // the step's index in the launch
@@ -194,6 +199,54 @@ struct NodesRolloutStep {
   __device__ __forceinline__ double* rew(const ScArgs& x) const { return x.rew + static_cast<int64_t>(k_) * x.n; }
   __device__ __forceinline__ bool write_back() const { return write_back_; }
 };
+
+// Step k of a closed-loop launch (sc_policy_rollout_nodes_kernel): a rollout step whose
+// action tile is not loaded but computed, from the observation tile the previous step left
+// (kPolicy: the parts of sc_nodes_tile that differ). Every output is optional; first() /
+// last(): the tile's first and last step in the launch, where obs_io is read and obs_io,
+// act_work and reward_sum are written.
+struct NodesPolicyStep {
+  static constexpr bool kKeepsState = true;
+  static constexpr bool kStreamOut = true;
+  static constexpr bool kObsOptional = true;
+  static constexpr bool kPolicy = true;
+  const ScPolicyLaunch& p;
+  int32_t t_, flags_;
+  uint32_t episode_;
+  int32_t k_;
+  bool keep_, write_back_, last_;
+  __device__ __forceinline__ int t() const { return t_; }
+  __device__ __forceinline__ int flags() const { return flags_; }
+  __device__ __forceinline__ uint32_t episode() const { return episode_; }
+  __device__ __forceinline__ const float* act(const ScArgs&) const { return nullptr; }  // never loaded
+  __device__ __forceinline__ bool keep_state() const { return keep_; }
+  template <class T>
+  __device__ __forceinline__ T* obs(const ScArgs& x) const {
+    return x.obs ? static_cast<T*>(x.obs) + static_cast<int64_t>(k_) * x.n * x.c.O : nullptr;
+  }
+  __device__ __forceinline__ void* term_obs(const ScArgs& x) const { return x.term_obs; }
+  __device__ __forceinline__ double* rew(const ScArgs& x) const {
+    return x.rew ? x.rew + static_cast<int64_t>(k_) * x.n : nullptr;
+  }
+  __device__ __forceinline__ float* actions(const ScArgs& x) const {
+    return p.actions_out ? p.actions_out + static_cast<int64_t>(k_) * x.n * x.c.A : nullptr;
+  }
+  __device__ __forceinline__ bool write_back() const { return write_back_; }
+  __device__ __forceinline__ bool first() const { return k_ == 0; }
+  __device__ __forceinline__ bool last() const { return last_; }
+};
+
+// The closed loop's product: wave w computes actions w, w + W, ... of its lane's env (n) from
+// the env's row of the observation tile into its row of the action tile. The observation
+// elements are LDS reads at an odd row stride (lanes on distinct banks); an action's parameter
+// words (O weights and the bias) are requested together, up to kNodesPolicyChunk per round.
+constexpr int kNodesPolicyChunk = 32;
+template <class ObsT>
+__device__ __forceinline__ void sc_nodes_policy_act(const ScPolicyView& pv, int A, int O, int64_t n, int w, int W,
+                                                    const ObsT* orow, float* arow) {
+  auto o = [&](int j) { return static_cast<float>(orow[j]); };
+  for (int q = w; q < A; q += W) arow[q] = sc_policy_action<kNodesPolicyChunk>(pv, O, n, q, o);
+}
 
 template <int MAXD, bool F64, bool LED, class Step>
 __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int lane, int w, int W, int E,
@@ -249,6 +302,21 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   auto sink = [&](int o, double x) { orow[o] = static_cast<ObsT>(x); };
   const NodesInbox in{ibtk + lane, ibval + lane, 64};
   const float* act = act_t + lane * Ap;
+  // closed loop: the call's rewards of wave 0's envs, added step by step (the ledger words'
+  // rows: a closed-loop launch keeps no ledgers)
+  [[maybe_unused]] double* const rsum = reinterpret_cast<double*>(lword);
+
+  if constexpr (Step::kPolicy) {
+    if (sp.first()) {  // the observation the envs last produced into the tile, then the first actions
+      __syncthreads();  // the block's previous tile is read (its last copy-out) until here
+      const ObsT* const src = static_cast<const ObsT*>(sp.p.obs_io) + n0 * c.O;
+      TileWalk tw(threadIdx.x, blockDim.x, c.O);
+      for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw.next()) obs_t[tw.r * Op + tw.k] = src[q];
+      if (w == 0 && live) rsum[lane] = sp.p.sum_add ? sp.p.reward_sum[n] : 0.0;
+      __syncthreads();
+      if (live) sc_nodes_policy_act(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap);
+    }
+  }
 
   // stage, one memory round: every thread requests its share of the tile's action rows
   // (one contiguous span), every wave its node's stocks, heap sizes and the first kStage
@@ -262,9 +330,11 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
     // the step server's state kept in LDS since its previous request (NodesServerStep)
     const bool keep = sp.keep_state();
     float av[kAct];
+    if constexpr (!Step::kPolicy) {  // (the closed loop's action tile is computed, not loaded)
 #pragma unroll
-    for (int u = 0; u < kAct; ++u)
-      if (static_cast<int>(threadIdx.x) + u * static_cast<int>(blockDim.x) < na) av[u] = src[threadIdx.x + u * blockDim.x];
+      for (int u = 0; u < kAct; ++u)
+        if (static_cast<int>(threadIdx.x) + u * static_cast<int>(blockDim.x) < na) av[u] = src[threadIdx.x + u * blockDim.x];
+    }
     const double r0 = (w == 0 && live && a.ep_ret && !keep) ? a.ep_ret[n] : 0.0;
     for (int i = w; i < NN; i += W)
       for (int p = 0; p < P; ++p) {
@@ -287,7 +357,7 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
                            lh, H, sz);
         bad |= !sc_recv_scan(lh, sz, sp.t(), recv[hp * 64 + lane]);
       }
-    {
+    if constexpr (!Step::kPolicy) {
       TileWalk tw(threadIdx.x, blockDim.x, c.A);
 #pragma unroll
       for (int u = 0; u < kAct; ++u, tw.next())
@@ -303,6 +373,22 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   bool flagged = (sp.flags() & 4) != 0;
   for (int v = 0; v < W; ++v) flagged |= amb[v * 64 + lane] != 0;
   const bool go = live && !flagged;
+
+  if constexpr (Step::kPolicy) {
+    // closed loop: the step's action rows out where asked (actions_out[k]; act_work at the
+    // launch's last step), one contiguous span per block like the observation rows; the
+    // barrier above published the tile, and nothing writes it before the step's third
+    float* const adst0 = sp.actions(a);
+    float* const adst1 = sp.last() ? sp.p.act_work : nullptr;
+    if (adst0 || adst1) {
+      TileWalk tw(threadIdx.x, blockDim.x, c.A);
+      for (int q = threadIdx.x; q < nb * c.A; q += blockDim.x, tw.next()) {
+        const float x = act_t[tw.r * Ap + tw.k];
+        if (adst0) __hip_atomic_store(&adst0[n0 * c.A + q], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (adst1) __hip_atomic_store(&adst1[n0 * c.A + q], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
 
   // act: every node at once (a node's act needs only what its own heaps release)
   if (go)
@@ -377,7 +463,12 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       for (int i = 0; i < NN; ++i) total = np_add(total, Num{cost_v[i * 64 + lane], cost_k[i * 64 + lane]});
       reward = np_neg(total).v;
     }
-    sp.rew(a)[n] = reward;
+    if constexpr (Step::kPolicy) {
+      if (double* const rw = sp.rew(a)) rw[n] = reward;
+      rsum[lane] = rsum[lane] + reward;
+    } else {
+      sp.rew(a)[n] = reward;
+    }
     if (a.ep_ret) {
       const double r = ret0[lane] + reward;  // episode_rewards += current_reward (:739)
       if (terminal && a.final_ret) a.final_ret[n] = r;
@@ -409,12 +500,21 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
     }
   }
   if (autoreset) {  // after the barrier every wave's heap copy-back has landed
+    // closed loop: wave 0 puts the reset observation into the tile as well (the policy's next
+    // input), once every thread has copied the terminal one out of it
+    if constexpr (Step::kPolicy) __syncthreads();
     if (w == 0 && live) {
       g.episode = sp.episode() + 1;
       g.led_v = nullptr;   // the ledger was restarted above
       sc_reset_env(c, g);  // heaps in HBM, stocks in the LDS copy
       ObsT* const robs = sp.template obs<ObsT>(a);
-      if (!Step::kObsOptional || robs) {
+      if constexpr (Step::kPolicy) {
+        auto both = [&](int o, double x) {
+          orow[o] = static_cast<ObsT>(x);
+          if (robs) robs[n * c.O + o] = static_cast<ObsT>(x);
+        };
+        sc_observe(c, g, 0, both);
+      } else if (!Step::kObsOptional || robs) {
         ObsRow out{robs, n * c.O, F64 ? 1 : 0};
         sc_observe(c, g, 0, out);
       }
@@ -431,6 +531,22 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       if constexpr (Step::kObsOptional) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
+  }
+  if constexpr (Step::kPolicy) {
+    // closed loop: the tile now holds the observation the envs produced (past the third
+    // barrier; at an auto-reset step the reset one, past the barrier just above) and no one
+    // reads this step's action tile any more: every wave computes its share of the next
+    // step's, which that step's first barrier publishes. The launch's last step writes the
+    // tile to obs_io instead, and wave 0 the rewards' sums.
+    if (sp.last()) {
+      ObsT* const dst = static_cast<ObsT*>(sp.p.obs_io) + n0 * c.O;
+      TileWalk tw2(threadIdx.x, blockDim.x, c.O);
+      for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw2.next())
+        __hip_atomic_store(&dst[q], obs_t[tw2.r * Op + tw2.k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (w == 0 && live) sp.p.reward_sum[n] = rsum[lane];
+    } else if (live) {
+      sc_nodes_policy_act(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap);
+    }
   }
   if (live) {  // the stocks of this wave's nodes back, one 64-env row per instruction (the
                // next tile's stage rewrites these rows: the same wave)
@@ -454,6 +570,12 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   // tile, a reloading one also its own stock, size and heap rows (the stock rows it stored
   // just above itself: same thread, same address, program order) and wave 0 ret0, which only
   // wave 0 reads.
+  // The closed loop (kPolicy) adds one writer and one reader to that picture: the next action
+  // tile is written past this step's last barrier (after every read of the current one) and
+  // read past the next step's first; the observation tile is read here, before that same
+  // barrier, past which the next step's act phase first writes it. A tile's first step in a
+  // launch opens with a barrier of its own before it overwrites the observation tile the
+  // block's previous tile may still be copying out.
 }
 
 // Four waves per SIMD (<= 128 VGPRs): two blocks of eight waves per CU, which is also what
@@ -545,6 +667,60 @@ void sc_rollout_nodes_kernel(const ScArgs a_arg, int W, int E, int K, int obs_mo
   }
 }
 
+// ---- closed-loop rollout: the rollout kernel with the action tile computed on chip --------
+// (scg_sc_rollout_policy, csrc/scg_sc_policy.h.) The rollout kernel's block, LDS layout,
+// persistent tile loop and step loop under NodesPolicyStep: a tile's first step in the launch
+// loads its envs' last observation rows (obs_io) into the observation tile and computes the
+// first action tile from it; after every other step each wave computes its share of the next
+// action tile from the observation tile the step just completed, so between two kept steps
+// nothing crosses HBM but the policy's parameter words (and the outputs asked for). The
+// launch's last step leaves obs_io, act_work, reward_sum and the state in HBM.
+struct ScPolicyKArgs {
+  ScArgs a;
+  ScPolicyLaunch p;
+};
+
+template <int MAXD, bool F64>
+__global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(kNodesWavesPerEu)))
+void sc_policy_rollout_nodes_kernel(const ScPolicyKArgs k_arg, int W, int E, int K) {
+  const int lane0 = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t n_tiles = (k_arg.a.n + 63) / 64;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    int32_t t = k_arg.a.t;
+    uint32_t episode = k_arg.a.episode;
+    bool keep = false;
+    for (int k = 0; k < K; ++k) {
+      // lane and launch arguments opaque per step, as in the rollout kernel
+      int lane;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane0));
+      typedef const __attribute__((address_space(4))) ScPolicyKArgs* KArgPtr;
+      KArgPtr ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(ap));
+      const ScPolicyKArgs& ka = *(const ScPolicyKArgs*)ap;
+      const ScArgs& a = ka.a;
+      const bool terminal = t == a.c.T;
+      const bool autoreset = terminal && (a.flags & 2);
+      const bool last = k == K - 1;
+      NodesPolicyStep sp{ka.p};
+      sp.t_ = t;
+      sp.flags_ = (terminal ? 1 : 0) | (autoreset ? 2 : 0) | (a.flags & 4);
+      sp.episode_ = episode;
+      sp.k_ = k;
+      sp.keep_ = keep;
+      sp.write_back_ = last || autoreset;
+      sp.last_ = last;
+      sc_nodes_tile<MAXD, F64, false>(a, tile, lane, w, W, E, sp);
+      keep = !autoreset;
+      if (autoreset) {
+        t = 1;
+        ++episode;
+      } else {
+        ++t;
+      }
+    }
+  }
+}
+
 // ---- step server for the drop-in SupplyChainEnv (include/scgpu.h scg_sc_server_*) --------
 // One block of the batch kernel's shape, resident: wave 0 polls the mailbox's request lines
 // (the request and the inline action row, lanes 0-31, system scope, with the exit word) and
@@ -571,6 +747,7 @@ struct NodesServerStep {
   static constexpr bool kKeepsState = true;
   static constexpr bool kStreamOut = false;  // host-mapped rows
   static constexpr bool kObsOptional = false;
+  static constexpr bool kPolicy = false;
   bool inline_act;
   template <class T>
   __device__ __forceinline__ T* obs(const ScArgs& x) const { return static_cast<T*>(x.obs); }
@@ -814,6 +991,40 @@ int sc_launch_nodes_rollout(const ScArgs& a, int maxd_bucket, int W, int E, int 
                    : sc_launch_nodes_rollout_d<D, false>(a, W, E, K, obs_mode, s);
   });
   if (!found) return fail(SCG_ERR_INVALID, "node-parallel rollout: nodes ship to at most 8 destinations");
+  return rc;
+}
+
+// K closed-loop steps of every env in one launch (sc_policy_rollout_nodes_kernel): the
+// rollout's block, LDS, persistent grid and block cap. a.act is unused; a.obs and a.rew may be
+// null (outputs nobody asked for).
+template <int MAXD, bool F64>
+int sc_launch_nodes_policy_d(const ScArgs& a, const ScPolicyLaunch& p, int W, int E, int K, hipStream_t s) {
+  const size_t lds = sc_nodes_lds_bytes(a.c.n_nodes, a.c.P, a.c.H, E, W, a.c.A, a.c.O, F64 ? 8 : 4);
+  if (lds > sc_nodes_lds_max()) return fail(SCG_ERR_INVALID, "closed-loop rollout: %zu B of LDS per block", lds);
+  int dev = 0;
+  if (!sc_nodes_allow_lds<&sc_policy_rollout_nodes_kernel<MAXD, F64>>(lds, sc_nodes_lds_max() - kNodesStaticLds, dev))
+    return fail(SCG_ERR_HIP, "closed-loop rollout: cannot raise its LDS limit");
+  const int64_t tiles = (a.n + 63) / 64;
+  int64_t blocks = tiles;
+  const int64_t resident = sc_nodes_resident_blocks<&sc_policy_rollout_nodes_kernel<MAXD, F64>>(dev, W, lds);
+  if (resident > 0 && resident < tiles) blocks = resident;
+  const int cap = g_nodes_max_blocks.load(std::memory_order_relaxed);
+  if (cap > 0 && cap < blocks) blocks = cap;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_policy_rollout_nodes_kernel<MAXD, F64>), dim3(static_cast<unsigned>(blocks)),
+                     dim3(64 * W), lds, s, ScPolicyKArgs{a, p}, W, E, K);
+  return check_launch("sc_policy_rollout_nodes_kernel");
+}
+
+int sc_launch_nodes_policy(const ScArgs& a, const ScPolicyLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
+  if (W < 1 || W > kNodesMaxWaves) return fail(SCG_ERR_INVALID, "closed-loop rollout: %d waves per block", W);
+  if (a.led_v) return fail(SCG_ERR_INVALID, "closed-loop rollout: no ledgers");
+  if (K < 1) return fail(SCG_ERR_INVALID, "closed-loop rollout: steps");
+  int rc = SCG_OK;
+  const bool found = sc_dispatch_maxd<8>(maxd_bucket, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    rc = a.obs_f64 ? sc_launch_nodes_policy_d<D, true>(a, p, W, E, K, s) : sc_launch_nodes_policy_d<D, false>(a, p, W, E, K, s);
+  });
+  if (!found) return fail(SCG_ERR_INVALID, "closed-loop rollout: nodes ship to at most 8 destinations");
   return rc;
 }
 

@@ -1,0 +1,98 @@
+// The SupplyChain linear policy, host and device (no HIP runtime header: a host program can
+// include this alone). It is the one place that knows the formula and the two layouts of the
+// parameters scg_sc_rollout_policy takes (include/scgpu.h, scg_sc_policy):
+//
+//   z_a = b_a;  for j = 0 .. O-1 ascending:  z_a = z_a + W[a][j] * o_j
+//   act_a = !(z_a >= lo) ? lo : (z_a > hi ? hi : z_a)
+//
+// for the observation o[0..O) the env last produced, as float32 (a float64 observation
+// element is rounded to float32 first: what a float32-observation env stores). Every multiply
+// and every add is rounded to float32 on its own (the units that include this are built with
+// -ffp-contract=off), in IEEE arithmetic, as NumPy computes the same loop; a NaN z gives lo.
+//
+// Word a*(O+1)+j of a policy is W[a][j] for j < O and b[a] for j == O. Per env the parameters
+// are float32 [A*(O+1)][N], env fastest, so a wave reads each word of its 64 envs as one
+// 256-byte row; shared they are float32 [A*(O+1)], one policy for every env. The same code
+// reads both through two strides: word q of env n is params[q * qstride + n * nstride], with
+// (qstride, nstride) = (N, 1) per env and (1, 0) shared.
+#pragma once
+
+#include <cstdint>
+
+#include "scgpu.h"
+
+#if defined(__HIPCC__)
+#define SCG_SC_POLICY_HD __host__ __device__ __attribute__((always_inline)) inline
+#else
+#define SCG_SC_POLICY_HD inline
+#endif
+
+namespace scg {
+
+// Parameter words of one policy, and the index of W[a][j] (j < O) or b[a] (j == O) among them.
+constexpr int sc_policy_words(int A, int O) { return A * (O + 1); }
+SCG_SC_POLICY_HD int sc_policy_word(int O, int a, int j) { return a * (O + 1) + j; }
+
+// The parameters as the formula reads them: the two strides and the clamp.
+struct ScPolicyView {
+  const float* params;
+  int64_t qstride, nstride;
+  float lo, hi;
+};
+
+SCG_SC_POLICY_HD ScPolicyView sc_policy_view(const float* params, bool shared, int64_t N, float lo, float hi) {
+  return shared ? ScPolicyView{params, 1, 0, lo, hi} : ScPolicyView{params, N, 1, lo, hi};
+}
+
+SCG_SC_POLICY_HD int64_t sc_policy_param_index(const ScPolicyView& pv, int O, int64_t n, int a, int j) {
+  return static_cast<int64_t>(sc_policy_word(O, a, j)) * pv.qstride + n * pv.nstride;
+}
+
+// A known kind and finite bounds lo <= hi (x - x is 0 only for a finite x).
+SCG_SC_POLICY_HD bool sc_policy_valid(int32_t kind, float lo, float hi) {
+  return kind == SCG_SC_POLICY_LINEAR && lo - lo == 0.0f && hi - hi == 0.0f && lo <= hi;
+}
+
+SCG_SC_POLICY_HD float sc_policy_clamp(float z, float lo, float hi) { return !(z >= lo) ? lo : (z > hi ? hi : z); }
+
+// Action a of env n from its observation obs(j), j = 0 .. O-1. The parameter words and the
+// observation elements are requested kChunk at a time, all of a chunk before the first is used
+// (one memory round per chunk instead of one dependent load per term), past the row's end
+// the last element again, so the requests are straight-line code; the sum itself runs in the
+// formula's order over the terms j < O alone.
+template <int kChunk, class Obs>
+SCG_SC_POLICY_HD float sc_policy_action(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs) {
+  const float* row = pv.params + sc_policy_param_index(pv, O, n, a, 0);
+  float z = row[static_cast<int64_t>(O) * pv.qstride];
+  for (int j0 = 0; j0 < O; j0 += kChunk) {
+    float wv[kChunk], ov[kChunk];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int u = 0; u < kChunk; ++u) {
+      const int j = j0 + u < O ? j0 + u : O - 1;
+      wv[u] = row[static_cast<int64_t>(j) * pv.qstride];
+      ov[u] = obs(j);
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int u = 0; u < kChunk; ++u) {
+      const float term = wv[u] * ov[u];
+      z = j0 + u < O ? z + term : z;
+    }
+  }
+  return sc_policy_clamp(z, pv.lo, pv.hi);
+}
+
+// What a closed-loop launch takes beside the step's launch arguments (scg_sc_nodes.hip).
+struct ScPolicyLaunch {
+  ScPolicyView pv;
+  void* obs_io;         // [N][O], obs dtype: read at the launch's first step, written at its last
+  float* act_work;      // [N][A]: the launch's last action rows
+  float* actions_out;   // [K][N][A] of this launch, or null
+  double* reward_sum;   // [N]
+  int32_t sum_add;      // 0: the launch stores its rewards' sum; else it adds to what is there
+};
+
+}  // namespace scg

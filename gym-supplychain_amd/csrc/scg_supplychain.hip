@@ -562,6 +562,11 @@ int sc_inbox_layout(const scg_sc_config* cfg, scg_sc_node* nodes) {
 }
 
 }  // namespace
+
+// The entry points' argument check and launch arguments, for scg_sc_policy.hip.
+int sc_host_check(const scg_sc_config* cfg, const scg_sc_state* st) { return sc_check(cfg, st); }
+ScArgs sc_host_args(const scg_sc_config* cfg, const scg_sc_state* st) { return sc_args(cfg, st); }
+
 }  // namespace scg
 
 using namespace scg;
@@ -850,6 +855,16 @@ static std::atomic<int> g_sc_rollout_chunk{0};
 int scg_sc_rollout_chunk(int32_t steps) {
   return g_sc_rollout_chunk.exchange(steps < 0 ? 0 : steps > SCG_SC_ROLLOUT_MAX ? SCG_SC_ROLLOUT_MAX : steps);
 }
+
+}  // extern "C"
+namespace scg {
+// Steps per launch of a fused rollout as the hook above set them (scg_sc_policy.hip).
+int sc_rollout_chunk_steps() {
+  const int hook = g_sc_rollout_chunk.load(std::memory_order_relaxed);
+  return hook > 0 ? hook : SCG_SC_ROLLOUT_MAX;
+}
+}  // namespace scg
+extern "C" {
 
 int scg_sc_rollout(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const float* actions, void* obs,
                    double* rewards, void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {

@@ -121,6 +121,15 @@ class BgPolicy(ctypes.Structure):
                 ("act_hi", ctypes.c_int32), ("params", ctypes.c_void_p)]
 
 
+SC_POLICY_LINEAR = 1
+
+
+class ScPolicy(ctypes.Structure):
+    """scg_sc_policy (include/scgpu.h): the linear policy of scg_sc_rollout_policy."""
+    _fields_ = [("kind", ctypes.c_int32), ("shared", ctypes.c_int32), ("act_lo", ctypes.c_float),
+                ("act_hi", ctypes.c_float), ("params", ctypes.c_void_p)]
+
+
 class BgServerLine(ctypes.Structure):
     """scg_bg_server_line (include/scgpu.h): one slot's 64-byte request line."""
     _fields_ = [("req_seq", ctypes.c_uint32), ("cmd", ctypes.c_int32), ("wpack", ctypes.c_uint32),
@@ -283,6 +292,12 @@ SIGNATURES = {
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_uint32, _i32p, ctypes.c_void_p]),
     "scg_sc_rollout_chunk": (ctypes.c_int, [ctypes.c_int32]),
+    "scg_sc_observe": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_void_p,
+                                      ctypes.c_void_p]),
+    "scg_sc_rollout_policy": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_int32,
+                                             ctypes.POINTER(ScPolicy), ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint32, _i32p, ctypes.c_void_p]),
     "scg_sc_draw_tables": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_uint32,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_nodes_max_blocks": (ctypes.c_int, [ctypes.c_int32]),

@@ -208,12 +208,34 @@ def _default_seed(seed, seed_group=None):
     return entropy_seed(seed, seed_group)
 
 
+class ScPackedPolicy:
+    """Linear policy parameters as scg_sc_rollout_policy reads them (SupplyChainVecEnv.pack_policy):
+    `params` float32 on the env's device, [A*(O+1), N] (a policy per env) or [A*(O+1)] (`shared`)."""
+    __slots__ = ("params", "shared", "n_envs", "n_actions", "n_obs")
+
+    def __init__(self, params, shared, n_envs, n_actions, n_obs):
+        self.params, self.shared, self.n_envs, self.n_actions, self.n_obs = params, shared, n_envs, n_actions, n_obs
+
+
+class ScPolicyRollout:
+    """What SupplyChainVecEnv.rollout_policy returns: `reward_sum` float64 [N], `last_obs`
+    [N, n_obs] (the env's own buffer: clone() to keep it), `dones` CPU bool [K], and `actions`
+    float32 [K, N, A], `obs` [K, N, n_obs], `rewards` float64 [K, N] where requested, else None."""
+    __slots__ = ("reward_sum", "last_obs", "dones", "actions", "obs", "rewards")
+
+    def __init__(self, reward_sum, last_obs, dones, actions=None, obs=None, rewards=None):
+        self.reward_sum, self.last_obs, self.dones = reward_sum, last_obs, dones
+        self.actions, self.obs, self.rewards = actions, obs, rewards
+
+
 class SupplyChainVecEnv:
     """N lock-step SupplyChainEnv instances on one GPU.
 
     reset() -> obs [N, n_obs]
     step(actions float32 [N, n_actions] in [-1, 1]) -> (obs, reward float64 [N], done bool [N], info)
     rollout(actions float32 [K, N, n_actions]) -> (obs [K, N, n_obs], rewards [K, N], dones [K]): K steps, one call
+    rollout_policy(weights, bias, n_steps) -> ScPolicyRollout: K steps with a linear policy's actions computed on the device
+    observe() -> obs [N, n_obs]: the current observation, whatever call left the state
 
     Returned tensors are this env's output buffers (clone() to keep them). With
     auto_reset the terminal step resets every env in the same kernel; info then holds
@@ -493,6 +515,118 @@ class SupplyChainVecEnv:
         if n_done.value:
             self.check_errors()
         return obs_out, rewards_out, dones
+
+    # closed loop: the current observation and the linear-policy rollout -------------------
+    def observe(self, out=None):
+        """The observation of the state as it stands [N, n_obs] (scg_sc_observe): what the
+        reset(), step() or rollout step that left this state returned — also after a rollout()
+        (which leaves step()'s buffers alone) or load_state_dict(). out: a contiguous tensor
+        of that shape and the env's obs dtype to fill instead of a new one."""
+        shape = (self.n_envs, self.n_obs)
+        if out is None:
+            out = torch.empty(shape, dtype=self.obs_dtype, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != self.obs_dtype or out.device != self.device or
+              tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous {self.obs_dtype} tensor {shape} on {self.device}")
+        nat.check(nat.lib.scg_sc_observe(self._cfg_ref, self._st_ref, out.data_ptr(), self._stream()))
+        return out
+
+    def _exact_f32(self, name, x, shapes):
+        """x as a float32 tensor on this env's device, of one of `shapes`; ValueError when the
+        shape is another or a value is not exactly a float32."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x))
+        if tuple(x.shape) not in shapes:
+            raise ValueError(f"{name} must have shape {' or '.join(str(list(s)) for s in shapes)}, "
+                             f"got {list(x.shape)}")
+        if x.dtype == torch.bool or x.dtype.is_complex:
+            raise ValueError(f"{name} must be real numbers, got {x.dtype}")
+        x = x.to(self.device)
+        if x.dtype != torch.float32:
+            y = x.to(torch.float32)
+            back = y.to(x.dtype)
+            if x.numel() and not bool(((back == x) | ((back != back) & (x != x))).all()):
+                raise ValueError(f"{name} ({x.dtype}) holds values that are not exactly float32")
+            x = y
+        return x
+
+    def pack_policy(self, weights, bias):
+        """Linear policy parameters in the layout scg_sc_rollout_policy reads, float32 on this
+        env's device: word a*(O+1)+j of a policy is weights[a][j] for j < O and bias[a] for
+        j == O. weights [N, A, O] with bias [N, A] or [A] (broadcast) packs a policy per env,
+        [A*(O+1), N] env fastest; weights [A, O] with bias [A] one shared policy [A*(O+1)].
+        Values must be exactly representable as float32 (ValueError otherwise). Pass the
+        result to rollout_policy() to pack once for many calls."""
+        N, A, O = self.n_envs, self.n_actions, self.n_obs
+        w = self._exact_f32("weights", weights, ((N, A, O), (A, O)))
+        shared = w.dim() == 2
+        b = self._exact_f32("bias", bias, ((A,),) if shared else ((N, A), (A,)))
+        if shared:
+            return ScPackedPolicy(torch.cat([w, b.unsqueeze(1)], dim=1).reshape(A * (O + 1)).contiguous(), True, N, A, O)
+        words = torch.cat([w, b.expand(N, A).unsqueeze(2)], dim=2).reshape(N, A * (O + 1))
+        return ScPackedPolicy(words.t().contiguous(), False, N, A, O)
+
+    def rollout_policy(self, weights, bias=None, n_steps=None, clip=None, return_actions=False, return_obs=False,
+                       return_rewards=False):
+        """n_steps steps with every env's action row computed on the device from the
+        observation o the env last produced (scg_sc_rollout_policy), all in float32, each
+        multiply and add rounded on its own, in this order:
+
+            z[a] = bias[a];  for j in range(n_obs): z[a] = z[a] + weights[a][j] * o[j]
+            action[a] = clip_lo if not z[a] >= clip_lo else min(z[a], clip_hi)
+
+        and everything else as rollout() of those actions gives it, bit for bit. weights / bias
+        as for pack_policy() (per env or shared), or weights a pack_policy() result and bias
+        None. clip (lo, hi), finite with lo <= hi; None: (-1, 1), the action space. The first
+        observation is observe() into the env's own buffer, so reset(), step(), rollout(),
+        rollout_policy() and load_state_dict() may precede this call in any order. Returns an
+        ScPolicyRollout. Errors as rollout(): past the terminal step without auto_reset raises
+        IndexError and leaves the env as it was; state_dict() afterwards resumes exactly.
+
+        On the node-parallel kernel without build_info the steps run in one launch (per 1024),
+        the product going from the step's observation tile to the next step's action tile in
+        LDS; every other kernel runs an action kernel and a step per step."""
+        N, A, O = self.n_envs, self.n_actions, self.n_obs
+        if isinstance(weights, ScPackedPolicy):
+            if bias is not None:
+                raise ValueError("a packed policy carries its bias")
+            packed = weights
+            if (packed.n_envs, packed.n_actions, packed.n_obs) != (N, A, O) or packed.params.device != self.device:
+                raise ValueError(f"the policy was packed for {packed.n_envs} envs, {packed.n_actions} actions and "
+                                 f"{packed.n_obs} observations on {packed.params.device}")
+        else:
+            packed = self.pack_policy(weights, bias)
+        if n_steps is None or isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)):
+            raise ValueError("n_steps must be an integer")
+        lo, hi = (-1.0, 1.0) if clip is None else clip
+        lo32, hi32 = np.float32(lo), np.float32(hi)
+        if not (np.isfinite(lo32) and np.isfinite(hi32) and lo32 <= hi32 and lo32 == lo and hi32 == hi):
+            raise ValueError(f"clip=({lo}, {hi}) must be finite float32 values with lo <= hi")
+        K = max(int(n_steps), 0)
+        dev = self.device
+        if getattr(self, "_pol_obs", None) is None:  # the call's own buffers, kept for the next
+            self._pol_obs = torch.empty((N, O), dtype=self.obs_dtype, device=dev)
+            self._pol_act = torch.empty((N, A), dtype=torch.float32, device=dev)
+        fused = self.kernel == "nodes" and not self.build_info
+        rewards = torch.empty((K, N), dtype=torch.float64, device=dev) if (return_rewards or not fused) else None
+        res = ScPolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), self._pol_obs, None,
+                              torch.empty((K, N, A), dtype=torch.float32, device=dev) if return_actions else None,
+                              torch.empty((K, N, O), dtype=self.obs_dtype, device=dev) if return_obs else None,
+                              rewards if return_rewards else None)
+        t0, T = self._st.time_step, self.spec.total_time_steps
+        if t0 >= 0:  # (before a reset the library refuses below)
+            self.observe(self._pol_obs)
+        pol = nat.ScPolicy(nat.SC_POLICY_LINEAR, int(packed.shared), float(lo32), float(hi32), packed.params.data_ptr())
+        n_done = ctypes.c_int32(0)
+        nat.check(nat.lib.scg_sc_rollout_policy(self._cfg_ref, self._st_ref, int(n_steps), ctypes.byref(pol),
+                                                self._pol_obs.data_ptr(), self._pol_act.data_ptr(),
+                                                nat.ptr(res.actions), nat.ptr(res.obs), nat.ptr(rewards),
+                                                res.reward_sum.data_ptr(), self._term_ptr, self._flags,
+                                                ctypes.byref(n_done), self._stream()))
+        res.dones = (torch.arange(t0 + 1, t0 + K + 1) % T) == 0
+        if n_done.value:
+            self.check_errors()
+        return res
 
     def _ledger_views(self, led, rewards):
         P, names = self.spec.P, nat.SC_LEDGER_NAMES

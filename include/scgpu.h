@@ -46,7 +46,9 @@ extern "C" {
  *   step kernel's launch constants (SCG_BG_STEP_CONSTS_BYTES).
  * 9: scg_sc_rollout (K SupplyChain steps per call, SCG_SC_ROLLOUT_MAX, SCG_SC_LAST_OBS) and
  *   the testing hook scg_sc_rollout_chunk; also scg_bg_rollout_policy (scg_bg_policy: the
- *   closed-loop BeerGame rollout with a per-env linear policy), an added entry point. */
+ *   closed-loop BeerGame rollout with a per-env linear policy), an added entry point; also
+ *   scg_sc_observe and scg_sc_rollout_policy (scg_sc_policy: the closed-loop SupplyChain
+ *   rollout with a linear policy, per env or shared), added entry points. */
 #define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
@@ -632,6 +634,68 @@ SCG_API int scg_sc_step(const scg_sc_config* cfg, scg_sc_state* st, const float*
 SCG_API int scg_sc_rollout(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const float* actions,
                            void* obs, double* rewards, void* terminal_obs, uint32_t flags, int32_t* n_done,
                            void* stream);
+
+/* The observation of the state as it stands, at st->time_step and st->episode: what the
+ * reset or step that left this state returned (a pure function of the stocks, the heaps, the
+ * time step and the episode's draws), for every kernel's layout. obs: DEVICE [N][n_obs] in
+ * the config's obs dtype. After scg_sc_rollout with SCG_SC_LAST_OBS off, or after a
+ * checkpoint was restored, this is how a caller learns the current observation.
+ * SCG_ERR_NOT_RESET before a reset. */
+SCG_API int scg_sc_observe(const scg_sc_config* cfg, const scg_sc_state* st, void* obs, void* stream);
+
+/*
+ * Closed-loop rollout: K steps per call as scg_sc_rollout runs them, with each env's action
+ * row computed on the device from the observation the env last produced (after an auto-reset
+ * inside the call, the reset observation) by a linear policy. For that observation o[0..O) as
+ * float32 (a float64 observation element is rounded to float32 first) and float32 parameters
+ * W[A][O], b[A]:
+ *   z_a = b_a;  for j = 0 .. O-1 ascending:  z_a = z_a + W[a][j] * o_j
+ *   act_a = !(z_a >= act_lo) ? act_lo : (z_a > act_hi ? act_hi : z_a)
+ * every multiply and add rounded to float32 on its own (no FMA), IEEE arithmetic; a NaN z
+ * gives act_lo (csrc/scg_sc_policy.h is the one definition, host and device).
+ * Word a*(O+1)+j of a policy is W[a][j] for j < O and b[a] for j == O. params is DEVICE
+ * float32 [A*(O+1)][N], env fastest (shared == 0: a policy per env, each word of a wave's 64
+ * envs one 256-byte row), or [A*(O+1)] (shared != 0: one policy for every env).
+ *
+ * The contract: the actions are the formula applied to the previous observation; everything
+ * else is what scg_sc_rollout would produce from those actions, bit for bit — observations,
+ * rewards, episode_return, final_return and terminal_obs, the error flag, the stocks, heap
+ * sizes and live heap entries in storage order, st->time_step and st->episode.
+ *   obs_io       DEVICE [N][n_obs], obs dtype, required: on entry the observation the envs last
+ *                produced (scg_sc_reset's, the last step's, or scg_sc_observe's), on return
+ *                the last step's
+ *   act_work     DEVICE float32 [N][n_actions], required scratch (the library allocates
+ *                nothing); on return the last step's action rows
+ *   actions_out  DEVICE float32 [K][N][n_actions], obs_out DEVICE [K][N][n_obs], rewards_out
+ *                DEVICE float64 [K][N]: each optional (NULL) on the fused path; the per-step
+ *                path needs rewards_out (a step's reward row has to land somewhere)
+ *   reward_sum   DEVICE float64 [N], required: the call's rewards added in step order
+ *                (s = 0.0; s = s + r_k), across auto-resets and launches; overwritten
+ *   terminal_obs, *n_done  as in scg_sc_rollout
+ *   flags        SCG_BG_AUTORESET | SCG_SC_SERIAL
+ * Every argument is checked before any HIP call, and a failed check leaves st untouched:
+ * SCG_ERR_INVALID (null policy, params, obs_io, act_work or reward_sum; unknown kind; bounds
+ * that are NaN, infinite or act_lo > act_hi; n_steps < 0; unknown flags), SCG_ERR_NOT_RESET,
+ * and without SCG_BG_AUTORESET SCG_ERR_PAST_HORIZON. n_steps == 0 clears reward_sum.
+ * Fused, under scg_sc_rollout's condition (a SCG_SC_KERNEL_NODES config on a state without
+ * ledgers): the rollout kernel's block, LDS and launches of up to SCG_SC_ROLLOUT_MAX steps,
+ * with the product running from the step's observation tile into the next step's action tile,
+ * both in LDS; with no output requested a kept step's only HBM traffic is the parameter reads.
+ * Every other config runs an action kernel and scg_sc_step per step: the same results, the
+ * per-step speed.
+ */
+#define SCG_SC_POLICY_LINEAR 1
+typedef struct scg_sc_policy {
+  int32_t kind;          /* SCG_SC_POLICY_LINEAR */
+  int32_t shared;        /* 0: params per env [A*(O+1)][N]; else one policy [A*(O+1)] */
+  float act_lo, act_hi;  /* finite, act_lo <= act_hi */
+  const float* params;   /* DEVICE float32 */
+} scg_sc_policy;
+
+SCG_API int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps,
+                                  const scg_sc_policy* policy, void* obs_io, float* act_work, float* actions_out,
+                                  void* obs_out, double* rewards_out, double* reward_sum, void* terminal_obs,
+                                  uint32_t flags, int32_t* n_done, void* stream);
 
 /* The per-episode tables scg_sc_step draws (for tests): demand DEVICE int32
  * [N][T+1][R][P], leadtimes DEVICE int32 [N][T][n_leadtimes] (NULL when deterministic). */

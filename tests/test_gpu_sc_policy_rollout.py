@@ -1,0 +1,288 @@
+"""SupplyChainVecEnv.rollout_policy (scg_sc_rollout_policy) and observe() (scg_sc_observe).
+
+The closed loop against its definition: the actions are the NumPy float32 formula applied to
+the previous observation, and everything else is what a twin env's open-loop rollout() of
+those actions gives — observations, rewards, terminal observation, returns, stocks, heap
+sizes, live heap entries in storage order, time step and episode. Every comparison is on the
+bits (torch.equal, array_equal on integer views); no tolerance is involved.
+
+Sizes: 130 envs (two full 64-env tiles and a 2-env tail), 7- to 12-step episodes, about 30
+steps (two auto-resets), the grid capped at one block (a block runs all three tiles) and
+launches cut at 5 steps (they end mid-episode)."""
+import numpy as np
+import pytest
+import torch
+
+from test_gpu_sc_rollout import DEV, STOCH, _actions, _pair, _same_state
+
+pytestmark = pytest.mark.gpu
+LO, HI = np.float32(-1.0), np.float32(1.0)
+
+
+@pytest.fixture(autouse=True)
+def small_launches():
+    """One block for every tile, launches of at most 5 steps."""
+    from gym_supplychain_amd import _native as nat
+    blocks = nat.lib.scg_sc_nodes_max_blocks(1)
+    chunk = nat.lib.scg_sc_rollout_chunk(5)
+    try:
+        yield
+    finally:
+        nat.lib.scg_sc_nodes_max_blocks(blocks)
+        nat.lib.scg_sc_rollout_chunk(chunk)
+
+
+def _params(env, shared=False, seed=3, n=None):
+    """Random float32 weights and biases, large enough for both clamps to bind now and then."""
+    n = env.n_envs if n is None else n
+    rng = np.random.default_rng(seed)
+    shape = () if shared else (n,)
+    w = rng.normal(0.0, 0.35, shape + (env.n_actions, env.n_obs)).astype(np.float32)
+    b = rng.normal(0.0, 0.5, shape + (env.n_actions,)).astype(np.float32)
+    return w, b
+
+
+def _formula(obs, w, b, lo=LO, hi=HI):
+    """The policy as scgpu.h states it, in NumPy float32: obs [N, O] -> actions [N, A]."""
+    o = obs.astype(np.float32)
+    n = o.shape[0]
+    w = np.broadcast_to(w, (n,) + w.shape[-2:])
+    z = np.broadcast_to(b, (n, w.shape[1])).astype(np.float32).copy()
+    with np.errstate(all="ignore"):
+        for j in range(o.shape[1]):
+            term = (w[:, :, j] * o[:, None, j]).astype(np.float32)
+            z = (z + term).astype(np.float32)
+        return np.where(~(z >= lo), lo, np.where(z > hi, hi, z)).astype(np.float32)
+
+
+def _bits(x):
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return np.ascontiguousarray(a).view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def _sequential_sum(rewards):
+    s = torch.zeros_like(rewards[0])
+    for r in rewards:
+        s = s + r
+    return s
+
+
+def _closed_loop_is_open_loop(env, twin, w, b, k, what="", clip=None):
+    """rollout_policy on env with every output; the twin rolls the actions it took."""
+    obs0 = env.observe().clone()
+    t0 = env.time_step
+    res = env.rollout_policy(torch.as_tensor(w), torch.as_tensor(b), k, clip=clip, return_actions=True, return_obs=True,
+                             return_rewards=True)
+    assert res.actions.dtype == torch.float32 and tuple(res.actions.shape) == (k, env.n_envs, env.n_actions)
+    assert res.obs.dtype == env.obs_dtype and res.rewards.dtype == torch.float64 and res.reward_sum.dtype == torch.float64
+    lo, hi = (LO, HI) if clip is None else (np.float32(clip[0]), np.float32(clip[1]))
+    prev = torch.cat([obs0[None], res.obs[:-1]]).cpu().numpy()
+    for j in range(k):
+        assert np.array_equal(_bits(res.actions[j]), _bits(_formula(prev[j], w, b, lo, hi))), (what, "actions of step", j)
+    obs, rew, dones = twin.rollout(res.actions)
+    assert torch.equal(res.obs, obs) and np.array_equal(_bits(res.rewards), _bits(rew)), what
+    assert torch.equal(res.dones, dones) and res.dones.device.type == "cpu", what
+    assert dones.tolist() == [(t0 + j + 1) % env.spec.total_time_steps == 0 for j in range(k)]
+    _same_state(env, twin, what)
+    assert torch.equal(env._term_obs, twin._term_obs), what
+    assert np.array_equal(_bits(res.reward_sum), _bits(_sequential_sum(rew))), what
+    assert torch.equal(res.last_obs, obs[-1]) and torch.equal(env.observe(), obs[-1]), what
+    assert torch.equal(env._pol_act, res.actions[-1]), what
+    env.check_errors()
+    return res
+
+
+CASES = {
+    "per_env_f32": dict(obs_dtype=torch.float32, total_time_steps=12),
+    "per_env_f64": dict(obs_dtype=torch.float64, total_time_steps=12),
+    "shared_f32": dict(obs_dtype=torch.float32, total_time_steps=11),
+    "shared_f64": dict(obs_dtype=torch.float64, total_time_steps=11),
+    "stochastic": dict(obs_dtype=torch.float32, total_time_steps=12, **STOCH),
+    "multiproduct": dict(scenario="sc-2perstage-multiproduct-v0", obs_dtype=torch.float32, total_time_steps=9),
+}
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_fused_closed_loop_is_the_formula_and_the_open_loop(case):
+    """Two auto-resets inside the call, launches ending mid-episode, three tiles on one block."""
+    env, twin = _pair(**CASES[case])
+    assert env.kernel == "nodes"
+    if case == "per_env_f32":
+        assert (env.n_actions, env.n_obs) == (14, 27)
+    w, b = _params(env, shared=case.startswith("shared"))
+    k = 30 if CASES[case]["total_time_steps"] > 9 else 25
+    res = _closed_loop_is_open_loop(env, twin, w, b, k, case)
+    assert int(res.dones.sum()) == 2 and env.episode == 2
+    acts = res.actions.cpu().numpy()
+    assert (acts == LO).any() and (acts == HI).any() and ((acts > LO) & (acts < HI)).any()  # the formula's three branches
+
+
+@pytest.mark.parametrize("kernel", ["lane", "staged", "level", "nodes_build_info"])
+def test_unfused_closed_loop_equals_the_fused_one(kernel):
+    """Every other config takes the action kernel and a step per step: the same twin test, and
+    the fused path's results."""
+    kw = dict(obs_dtype=torch.float32, total_time_steps=12, **STOCH)
+    if kernel == "nodes_build_info":
+        env, twin = _pair(kernel="nodes", build_info=True, **kw)
+        assert env.kernel == "nodes" and env.build_info
+    else:
+        env, twin = _pair(kernel=kernel, **kw)
+        assert env.kernel == kernel
+    fused = _pair(**kw)[0]
+    w, b = _params(env)
+    res = _closed_loop_is_open_loop(env, twin, w, b, 30, kernel)
+    ref = fused.rollout_policy(torch.as_tensor(w), torch.as_tensor(b), 30, return_actions=True, return_obs=True,
+                               return_rewards=True)
+    for name in ("actions", "obs", "rewards", "reward_sum", "last_obs"):
+        assert np.array_equal(_bits(getattr(res, name)), _bits(getattr(ref, name))), (kernel, name)
+    assert torch.equal(env.stock, fused.stock) and torch.equal(env.final_return, fused.final_return)
+    if kernel == "nodes_build_info":
+        assert torch.equal(env._led, twin._led) and torch.equal(env._fled, twin._fled)
+
+
+def test_serial_walk_gives_the_same_results():
+    kw = dict(obs_dtype=torch.float32, total_time_steps=12, **STOCH)
+    env, twin = _pair(serial=True, **kw)
+    plain = _pair(**kw)[0]
+    w, b = _params(env)
+    res = _closed_loop_is_open_loop(env, twin, w, b, 30, "serial")
+    ref = plain.rollout_policy(torch.as_tensor(w), torch.as_tensor(b), 30, return_actions=True, return_obs=True)
+    assert torch.equal(res.actions, ref.actions) and torch.equal(res.obs, ref.obs)
+    assert np.array_equal(_bits(res.reward_sum), _bits(ref.reward_sum))
+    _same_state(env, plain, "serial against node-parallel")
+
+
+@pytest.mark.parametrize("start", ["steps", "rollout", "checkpoint"])
+def test_start_mid_episode(start):
+    """After three step() calls, after a rollout(), and after load_state_dict() of a checkpoint
+    taken mid-episode (a checkpoint holds no observation: observe() supplies it)."""
+    import gym_supplychain_amd as gsa
+    kw = dict(obs_dtype=torch.float32, total_time_steps=10)
+    env, twin = _pair(**kw)
+    pre = _actions(env, 3)
+    if start == "steps":
+        for e in (env, twin):
+            for a in pre:
+                e.step(a)
+    else:
+        for e in (env, twin):
+            e.rollout(pre)
+    if start == "checkpoint":
+        fresh = gsa.make_vec("sc-2perstage-v0", env.n_envs, seed=99, device=DEV, kernel="nodes", **kw)
+        fresh.load_state_dict(env.state_dict())
+        env = fresh
+    assert env.time_step == 3
+    w, b = _params(env)
+    _closed_loop_is_open_loop(env, twin, w, b, 12, start)
+    resumed = gsa.make_vec("sc-2perstage-v0", env.n_envs, seed=7, device=DEV, kernel="nodes", **kw)
+    resumed.load_state_dict(env.state_dict())  # state_dict() after the closed loop resumes exactly
+    _closed_loop_is_open_loop(resumed, twin, w, b, 9, start + ", resumed")
+    assert (resumed.time_step, resumed.episode) == (4, 2)
+
+
+def test_outputs_are_optional():
+    """With none requested the state and reward_sum are the full-output run's; a packed policy
+    serves both calls, and a shared one packs to one row."""
+    full, bare = _pair(obs_dtype=torch.float32, total_time_steps=12, **STOCH)
+    w, b = _params(full)
+    packed = full.pack_policy(w, b)
+    assert not packed.shared and tuple(packed.params.shape) == (14 * 28, 130) and packed.params.dtype == torch.float32
+    assert torch.equal(packed.params[3 * 28 + 5], torch.as_tensor(w[:, 3, 5], device=DEV))
+    assert torch.equal(packed.params[3 * 28 + 27], torch.as_tensor(b[:, 3], device=DEV))
+    a = full.rollout_policy(packed, n_steps=30, return_actions=True, return_obs=True, return_rewards=True)
+    c = bare.rollout_policy(packed, n_steps=30)
+    assert c.actions is None and c.obs is None and c.rewards is None
+    assert np.array_equal(_bits(a.reward_sum), _bits(c.reward_sum)) and torch.equal(a.last_obs, c.last_obs)
+    assert torch.equal(c.dones, a.dones)
+    _same_state(full, bare, "no outputs")
+    assert torch.equal(full._term_obs, bare._term_obs)
+    ws, bs = _params(full, shared=True)
+    one = full.pack_policy(ws, bs)
+    assert one.shared and tuple(one.params.shape) == (14 * 28,)
+    with pytest.raises(ValueError):
+        full.pack_policy(w.astype(np.float64) + 1e-12, b)  # not float32 values
+    with pytest.raises(ValueError):
+        full.pack_policy(w[:, :, :-1], b)
+    with pytest.raises(ValueError):
+        full.rollout_policy(packed, n_steps=2, clip=(1.0, -1.0))
+    with pytest.raises(ValueError):
+        full.rollout_policy(packed, n_steps=2, clip=(0.0, float("inf")))
+    zero = full.rollout_policy(packed, n_steps=0)
+    assert not zero.reward_sum.any() and zero.dones.numel() == 0
+    _same_state(full, bare, "a rollout of no steps")
+
+
+def test_narrow_clip_and_equal_bounds():
+    env, twin = _pair(obs_dtype=torch.float32, total_time_steps=8)
+    w, b = _params(env)
+    _closed_loop_is_open_loop(env, twin, w, b, 6, "clip", clip=(-0.25, 0.5))
+    res = _closed_loop_is_open_loop(env, twin, w, b, 5, "lo == hi", clip=(0.125, 0.125))
+    assert bool((res.actions == 0.125).all())
+
+
+def test_shards_equal_the_whole_batch():
+    """Two envs of 65 with env_offset 0 / 65 and the matching slices of the per-env parameters."""
+    kw = dict(obs_dtype=torch.float32, total_time_steps=12, **STOCH)
+    whole = _pair(**kw)[0]
+    parts = [_pair(n=65, env_offset=off, **kw)[0] for off in (0, 65)]
+    w, b = _params(whole)
+    ref = whole.rollout_policy(torch.as_tensor(w), torch.as_tensor(b), 30, return_actions=True, return_obs=True)
+    got = [p.rollout_policy(torch.as_tensor(w[i * 65:(i + 1) * 65]), torch.as_tensor(b[i * 65:(i + 1) * 65]), 30,
+                            return_actions=True, return_obs=True) for i, p in enumerate(parts)]
+    assert torch.equal(torch.cat([g.actions for g in got], dim=1), ref.actions)
+    assert torch.equal(torch.cat([g.obs for g in got], dim=1), ref.obs)
+    assert np.array_equal(_bits(torch.cat([g.reward_sum for g in got])), _bits(ref.reward_sum))
+    assert torch.equal(torch.cat([p.stock for p in parts]), whole.stock)
+    assert torch.equal(torch.cat([p._heap_size for p in parts], dim=1), whole._heap_size)
+    assert torch.equal(torch.cat([p.final_return for p in parts]), whole.final_return)
+
+
+@pytest.mark.parametrize("obs_dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("kernel", ["lane", "level", "staged", "nodes"])
+def test_observe_is_what_the_last_call_returned(kernel, obs_dtype):
+    """reset(), every step() (the terminal one included, with and without auto-reset) and the
+    last row of a rollout()."""
+    kw = dict(kernel=kernel, obs_dtype=obs_dtype, total_time_steps=7, **STOCH)
+    env, plain = _pair(**kw)[0], _pair(auto_reset=False, **kw)[0]
+    for e in (env, plain):
+        assert e.kernel == kernel
+        first = e.reset()
+        out = torch.empty_like(first)
+        assert e.observe(out) is out and torch.equal(out, first)
+        for j, a in enumerate(_actions(e, 7)):
+            obs, _, done, _ = e.step(a)
+            assert bool(done.all()) == (j == 6)
+            assert torch.equal(e.observe(), obs), (kernel, "step", j)
+        assert e.time_step == (0 if e.auto_reset else 7)
+    obs, _, _ = env.rollout(_actions(env, 10, seed=12))
+    assert torch.equal(env.observe(), obs[-1]) and env.time_step == 3
+    plain.reset()
+    obs, _, dones = plain.rollout(_actions(plain, 7, seed=13))
+    assert dones.tolist() == [False] * 6 + [True] and torch.equal(plain.observe(), obs[-1])
+    with pytest.raises(ValueError):
+        env.observe(torch.empty((env.n_envs, env.n_obs + 1), dtype=obs_dtype, device=DEV))
+
+
+def test_observe_and_rollout_policy_before_reset():
+    import gym_supplychain_amd as gsa
+    env = gsa.make_vec("sc-2perstage-v0", 130, seed=5, device=DEV, kernel="nodes", total_time_steps=7)
+    w, b = _params(env, shared=True)
+    with pytest.raises(RuntimeError):
+        env.observe()
+    with pytest.raises(RuntimeError):
+        env.rollout_policy(w, b, 3)
+
+
+def test_past_the_horizon_without_auto_reset_changes_nothing():
+    env, twin = _pair(auto_reset=False, obs_dtype=torch.float32)
+    w, b = _params(env)
+    for e in (env, twin):
+        e.rollout(_actions(e, 2))
+    with pytest.raises(IndexError):
+        env.rollout_policy(w, b, 6)  # 2 + 6 steps of a 7-step episode
+    _same_state(env, twin, "after the refused call")
+    assert torch.equal(env._heap_tk, twin._heap_tk) and torch.equal(env._heap_val, twin._heap_val)
+    _closed_loop_is_open_loop(env, twin, w, b, 5, "to the terminal step")
+    assert env.time_step == 7
+    with pytest.raises(IndexError):
+        env.rollout_policy(w, b, 1)
