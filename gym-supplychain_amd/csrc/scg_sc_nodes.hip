@@ -28,11 +28,11 @@
 // node after node in the reference's order (sc_nodes_serial). Observations and actions go
 // through LDS tiles so HBM sees whole rows; the state pointers stay the batch's base
 // pointers (ScEnv soff/hoff) so they live in SGPRs.
-// The same tile code runs under three more drivers: the rollout kernel (a step loop inside the
-// tile loop, the state in LDS between a launch's steps), the closed-loop rollout kernel (the
-// same, with each step's action tile computed from the previous step's observation tile by a
-// linear policy, scg_sc_policy.h) and the step server (one resident block serving a drop-in
-// env's steps).
+// The same tile code runs under four more drivers: the rollout kernel (a step loop inside the
+// tile loop, the state in LDS between a launch's steps), the two closed-loop rollout kernels
+// (the same, with each step's action tile computed from the previous step's observation tile
+// by a linear policy, scg_sc_policy.h, or a one-hidden-layer ReLU policy, scg_sc_mlp.h) and the
+// step server (one resident block serving a drop-in env's steps).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -75,6 +75,7 @@ struct ScAcc {  // a marker: a non-null ScEnv::dbg turns the section stamps on
 #include "scg_supplychain_args.h"
 #include "scg_supplychain_nodes.h"
 #include "scg_sc_policy.h"
+#include "scg_sc_mlp.h"
 
 // Diagnostic build only (-DSCG_NODES_STAMPS, tools/nodes_stamps.py): lane 0 of every wave
 // records the shader clock at the phase boundaries (0 start, 5 heaps staged, 6 past the first
@@ -200,17 +201,20 @@ struct NodesRolloutStep {
   __device__ __forceinline__ bool write_back() const { return write_back_; }
 };
 
-// Step k of a closed-loop launch (sc_policy_rollout_nodes_kernel): a rollout step whose
-// action tile is not loaded but computed, from the observation tile the previous step left
-// (kPolicy: the parts of sc_nodes_tile that differ). Every output is optional; first() /
-// last(): the tile's first and last step in the launch, where obs_io is read and obs_io,
-// act_work and reward_sum are written.
-struct NodesPolicyStep {
+// Step k of a closed-loop launch (sc_policy_rollout_nodes_kernel, sc_mlp_rollout_nodes_kernel):
+// a rollout step whose action tile is not loaded but computed, from the observation tile the
+// previous step left (kPolicy: the parts of sc_nodes_tile that differ), by the policy Launch
+// carries (ScPolicyLaunch: linear; ScMlpLaunch: one hidden layer). Every output is optional;
+// first() / last(): the tile's first and last step in the launch, where obs_io is read and
+// obs_io, act_work and reward_sum are written.
+template <class Launch>
+struct NodesClosedStep {
   static constexpr bool kKeepsState = true;
   static constexpr bool kStreamOut = true;
   static constexpr bool kObsOptional = true;
   static constexpr bool kPolicy = true;
-  const ScPolicyLaunch& p;
+  static constexpr bool kMlp = std::is_same<Launch, ScMlpLaunch>::value;
+  const Launch& p;
   int32_t t_, flags_;
   uint32_t episode_;
   int32_t k_;
@@ -235,6 +239,8 @@ struct NodesPolicyStep {
   __device__ __forceinline__ bool first() const { return k_ == 0; }
   __device__ __forceinline__ bool last() const { return last_; }
 };
+using NodesPolicyStep = NodesClosedStep<ScPolicyLaunch>;
+using NodesMlpStep = NodesClosedStep<ScMlpLaunch>;
 
 // The closed loop's product: wave w computes actions w, w + W, ... of its lane's env (n) from
 // the env's row of the observation tile into its row of the action tile. The observation
@@ -246,6 +252,27 @@ __device__ __forceinline__ void sc_nodes_policy_act(const ScPolicyView& pv, int 
                                                     const ObsT* orow, float* arow) {
   auto o = [&](int j) { return static_cast<float>(orow[j]); };
   for (int q = w; q < A; q += W) arow[q] = sc_policy_action<kNodesPolicyChunk>(pv, O, n, q, o);
+}
+
+// The closed loop's MLP (kMlp steps): wave w computes hidden units w, w + W, ... of its lane's
+// env from the env's row of the observation tile into the hidden tile [H][64] (float, unit-major,
+// lane fastest: the lanes of a wave on consecutive banks; `hid` is the lane's column); past a
+// barrier it computes actions w, w + W, ... from that column into the env's row of the action
+// tile. Every thread of the block calls it (live: the lane has an env). The hidden tile lies
+// over the inbox values and the cost rows, idle where this runs (the note at the end of
+// sc_nodes_tile); the launcher admits only H <= 2 * (E + NN).
+template <class ObsT>
+__device__ __forceinline__ void sc_nodes_mlp_act(const ScMlpView& mv, int A, int O, int64_t n, bool live, int w, int W,
+                                                 const ObsT* orow, float* arow, float* hid) {
+  if (live) {
+    auto o = [&](int j) { return static_cast<float>(orow[j]); };
+    for (int i = w; i < mv.H; i += W) hid[i * 64] = sc_mlp_hidden<kNodesPolicyChunk>(mv, O, n, i, o);
+  }
+  __syncthreads();
+  if (live) {
+    auto h = [&](int i) { return hid[i * 64]; };
+    for (int q = w; q < A; q += W) arow[q] = sc_mlp_action<kNodesPolicyChunk>(mv, O, n, q, h);
+  }
 }
 
 template <int MAXD, bool F64, bool LED, class Step>
@@ -314,7 +341,12 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw.next()) obs_t[tw.r * Op + tw.k] = src[q];
       if (w == 0 && live) rsum[lane] = sp.p.sum_add ? sp.p.reward_sum[n] : 0.0;
       __syncthreads();
-      if (live) sc_nodes_policy_act(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap);
+      if constexpr (Step::kMlp) {
+        sc_nodes_mlp_act(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap,
+                         reinterpret_cast<float*>(ibval) + lane);
+      } else if (live) {
+        sc_nodes_policy_act(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap);
+      }
     }
   }
 
@@ -544,6 +576,8 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw2.next())
         __hip_atomic_store(&dst[q], obs_t[tw2.r * Op + tw2.k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (w == 0 && live) sp.p.reward_sum[n] = rsum[lane];
+    } else if constexpr (Step::kMlp) {
+      sc_nodes_mlp_act(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap, reinterpret_cast<float*>(ibval) + lane);
     } else if (live) {
       sc_nodes_policy_act(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap);
     }
@@ -576,6 +610,26 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   // barrier, past which the next step's act phase first writes it. A tile's first step in a
   // launch opens with a barrier of its own before it overwrites the observation tile the
   // block's previous tile may still be copying out.
+  // The MLP closed loop keeps its hidden tile [H][64] (float) over ibval and cost_v, which are
+  // adjacent: (E + NN) * 512 bytes, H <= 2 * (E + NN) units (sc_mlp_fused_hidden_max; the
+  // launcher refuses more). It is written and read only inside sc_nodes_mlp_act, i.e. at
+  // first() past the obs_io load's barrier and after a step's last barrier (the auto-reset
+  // one included). That is safe because
+  //  - the region's last read in a step lies before that step's last barrier: ibval by the
+  //    heaps phase (sc_nodes_heap's inbox pushes) and wave 0's serial walk, cost_v by wave 0's
+  //    reward sum; nothing after the barrier (copy-out, reset, obs_io / reward_sum stores,
+  //    stock write-back) names either;
+  //  - no stage writes it: a kept or reloading stage writes recv, amb, the action tile (not
+  //    even that in a closed loop), the wave's own stk / hsz / heap rows and ret0;
+  //  - its next write is the next step's act phase (in.ship's values, cost_v), past that
+  //    step's first barrier, which no wave passes before every wave has left
+  //    sc_nodes_mlp_act; an inbox value is read only under a time word (ibtk, not
+  //    overlaid) >= 0, and every time word is cleared and every shipped value written in the
+  //    same act phase (or serial walk) before it is read, so no stale value under the hidden
+  //    tile is ever used;
+  //  - the reset path (sc_reset_env, sc_observe) touches the HBM heaps and sizes, stk and the
+  //    observation tile only.
+  // stk starts right behind cost_v: a hidden tile wider than the bound would overwrite stocks.
 }
 
 // Four waves per SIMD (<= 128 VGPRs): two blocks of eight waves per CU, which is also what
@@ -675,9 +729,20 @@ void sc_rollout_nodes_kernel(const ScArgs a_arg, int W, int E, int K, int obs_mo
 // action tile from the observation tile the step just completed, so between two kept steps
 // nothing crosses HBM but the policy's parameter words (and the outputs asked for). The
 // launch's last step leaves obs_io, act_work, reward_sum and the state in HBM.
+// The one-hidden-layer policy (scg_sc_rollout_mlp, csrc/scg_sc_mlp.h) runs the same loops in a
+// kernel of its own, sc_mlp_rollout_nodes_kernel, under NodesMlpStep: where the linear step
+// computes its action tile, every wave first computes its share of the hidden units into a
+// tile over LDS the step leaves idle there (sc_nodes_mlp_act; the note at the end of
+// sc_nodes_tile), so the block's LDS is the linear kernel's. (The step loop is written out in
+// each rollout kernel: moved into a shared inline function it compiled to other code for the
+// linear kernel, whose instruction counts are pinned.)
 struct ScPolicyKArgs {
   ScArgs a;
   ScPolicyLaunch p;
+};
+struct ScMlpKArgs {
+  ScArgs a;
+  ScMlpLaunch p;
 };
 
 template <int MAXD, bool F64>
@@ -702,6 +767,47 @@ void sc_policy_rollout_nodes_kernel(const ScPolicyKArgs k_arg, int W, int E, int
       const bool autoreset = terminal && (a.flags & 2);
       const bool last = k == K - 1;
       NodesPolicyStep sp{ka.p};
+      sp.t_ = t;
+      sp.flags_ = (terminal ? 1 : 0) | (autoreset ? 2 : 0) | (a.flags & 4);
+      sp.episode_ = episode;
+      sp.k_ = k;
+      sp.keep_ = keep;
+      sp.write_back_ = last || autoreset;
+      sp.last_ = last;
+      sc_nodes_tile<MAXD, F64, false>(a, tile, lane, w, W, E, sp);
+      keep = !autoreset;
+      if (autoreset) {
+        t = 1;
+        ++episode;
+      } else {
+        ++t;
+      }
+    }
+  }
+}
+
+template <int MAXD, bool F64>
+__global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(kNodesWavesPerEu)))
+void sc_mlp_rollout_nodes_kernel(const ScMlpKArgs k_arg, int W, int E, int K) {
+  const int lane0 = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t n_tiles = (k_arg.a.n + 63) / 64;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    int32_t t = k_arg.a.t;
+    uint32_t episode = k_arg.a.episode;
+    bool keep = false;
+    for (int k = 0; k < K; ++k) {
+      // lane and launch arguments opaque per step, as in the rollout kernel
+      int lane;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane0));
+      typedef const __attribute__((address_space(4))) ScMlpKArgs* KArgPtr;
+      KArgPtr ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(ap));
+      const ScMlpKArgs& ka = *(const ScMlpKArgs*)ap;
+      const ScArgs& a = ka.a;
+      const bool terminal = t == a.c.T;
+      const bool autoreset = terminal && (a.flags & 2);
+      const bool last = k == K - 1;
+      NodesMlpStep sp{ka.p};
       sp.t_ = t;
       sp.flags_ = (terminal ? 1 : 0) | (autoreset ? 2 : 0) | (a.flags & 4);
       sp.episode_ = episode;
@@ -994,38 +1100,59 @@ int sc_launch_nodes_rollout(const ScArgs& a, int maxd_bucket, int W, int E, int 
   return rc;
 }
 
-// K closed-loop steps of every env in one launch (sc_policy_rollout_nodes_kernel): the
-// rollout's block, LDS, persistent grid and block cap. a.act is unused; a.obs and a.rew may be
-// null (outputs nobody asked for).
-template <int MAXD, bool F64>
-int sc_launch_nodes_policy_d(const ScArgs& a, const ScPolicyLaunch& p, int W, int E, int K, hipStream_t s) {
+// K closed-loop steps of every env in one launch (kKernel: sc_policy_rollout_nodes_kernel or
+// sc_mlp_rollout_nodes_kernel of the launch's policy): the rollout's block, LDS, persistent
+// grid and block cap. a.act is unused; a.obs and a.rew may be null (outputs nobody asked for).
+template <auto kKernel, bool F64, class KArgs, class Launch>
+int sc_launch_nodes_closed_d(const ScArgs& a, const Launch& p, int W, int E, int K, hipStream_t s, const char* name) {
   const size_t lds = sc_nodes_lds_bytes(a.c.n_nodes, a.c.P, a.c.H, E, W, a.c.A, a.c.O, F64 ? 8 : 4);
   if (lds > sc_nodes_lds_max()) return fail(SCG_ERR_INVALID, "closed-loop rollout: %zu B of LDS per block", lds);
   int dev = 0;
-  if (!sc_nodes_allow_lds<&sc_policy_rollout_nodes_kernel<MAXD, F64>>(lds, sc_nodes_lds_max() - kNodesStaticLds, dev))
+  if (!sc_nodes_allow_lds<kKernel>(lds, sc_nodes_lds_max() - kNodesStaticLds, dev))
     return fail(SCG_ERR_HIP, "closed-loop rollout: cannot raise its LDS limit");
   const int64_t tiles = (a.n + 63) / 64;
   int64_t blocks = tiles;
-  const int64_t resident = sc_nodes_resident_blocks<&sc_policy_rollout_nodes_kernel<MAXD, F64>>(dev, W, lds);
+  const int64_t resident = sc_nodes_resident_blocks<kKernel>(dev, W, lds);
   if (resident > 0 && resident < tiles) blocks = resident;
   const int cap = g_nodes_max_blocks.load(std::memory_order_relaxed);
   if (cap > 0 && cap < blocks) blocks = cap;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(sc_policy_rollout_nodes_kernel<MAXD, F64>), dim3(static_cast<unsigned>(blocks)),
-                     dim3(64 * W), lds, s, ScPolicyKArgs{a, p}, W, E, K);
-  return check_launch("sc_policy_rollout_nodes_kernel");
+  hipLaunchKernelGGL(kKernel, dim3(static_cast<unsigned>(blocks)), dim3(64 * W), lds, s, KArgs{a, p}, W, E, K);
+  return check_launch(name);
 }
 
-int sc_launch_nodes_policy(const ScArgs& a, const ScPolicyLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
+template <class Launch>
+int sc_launch_nodes_closed(const ScArgs& a, const Launch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
+  constexpr bool kMlp = std::is_same<Launch, ScMlpLaunch>::value;
   if (W < 1 || W > kNodesMaxWaves) return fail(SCG_ERR_INVALID, "closed-loop rollout: %d waves per block", W);
   if (a.led_v) return fail(SCG_ERR_INVALID, "closed-loop rollout: no ledgers");
   if (K < 1) return fail(SCG_ERR_INVALID, "closed-loop rollout: steps");
   int rc = SCG_OK;
   const bool found = sc_dispatch_maxd<8>(maxd_bucket, [&](auto d) {
     constexpr int D = decltype(d)::value;
-    rc = a.obs_f64 ? sc_launch_nodes_policy_d<D, true>(a, p, W, E, K, s) : sc_launch_nodes_policy_d<D, false>(a, p, W, E, K, s);
+    constexpr const char* name = kMlp ? "sc_mlp_rollout_nodes_kernel" : "sc_policy_rollout_nodes_kernel";
+    if constexpr (kMlp) {
+      rc = a.obs_f64 ? sc_launch_nodes_closed_d<&sc_mlp_rollout_nodes_kernel<D, true>, true, ScMlpKArgs>(a, p, W, E, K, s, name)
+                     : sc_launch_nodes_closed_d<&sc_mlp_rollout_nodes_kernel<D, false>, false, ScMlpKArgs>(a, p, W, E, K, s, name);
+    } else {
+      rc = a.obs_f64
+               ? sc_launch_nodes_closed_d<&sc_policy_rollout_nodes_kernel<D, true>, true, ScPolicyKArgs>(a, p, W, E, K, s, name)
+               : sc_launch_nodes_closed_d<&sc_policy_rollout_nodes_kernel<D, false>, false, ScPolicyKArgs>(a, p, W, E, K, s, name);
+    }
   });
   if (!found) return fail(SCG_ERR_INVALID, "closed-loop rollout: nodes ship to at most 8 destinations");
   return rc;
+}
+
+int sc_launch_nodes_policy(const ScArgs& a, const ScPolicyLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
+  return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);
+}
+
+// The hidden tile lies over the inbox values and cost rows of the block's LDS (sc_nodes_tile):
+// a wider one would run into the stocks behind them.
+int sc_launch_nodes_mlp(const ScArgs& a, const ScMlpLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
+  if (p.pv.H < 1 || p.pv.H > sc_mlp_fused_hidden_max(E, a.c.n_nodes))
+    return fail(SCG_ERR_INVALID, "closed-loop rollout: %d hidden units do not fit the block's idle LDS", p.pv.H);
+  return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);
 }
 
 // The step server's block for a config the batch kernel runs (float64 observations, no

@@ -48,51 +48,62 @@ SCG_SC_POLICY_HD int64_t sc_policy_param_index(const ScPolicyView& pv, int O, in
   return static_cast<int64_t>(sc_policy_word(O, a, j)) * pv.qstride + n * pv.nstride;
 }
 
-// A known kind and finite bounds lo <= hi (x - x is 0 only for a finite x).
+// Finite bounds lo <= hi (x - x is 0 only for a finite x); with a known kind, a valid policy.
+SCG_SC_POLICY_HD bool sc_policy_bounds_valid(float lo, float hi) { return lo - lo == 0.0f && hi - hi == 0.0f && lo <= hi; }
 SCG_SC_POLICY_HD bool sc_policy_valid(int32_t kind, float lo, float hi) {
-  return kind == SCG_SC_POLICY_LINEAR && lo - lo == 0.0f && hi - hi == 0.0f && lo <= hi;
+  return kind == SCG_SC_POLICY_LINEAR && sc_policy_bounds_valid(lo, hi);
 }
 
 SCG_SC_POLICY_HD float sc_policy_clamp(float z, float lo, float hi) { return !(z >= lo) ? lo : (z > hi ? hi : z); }
 
-// Action a of env n from its observation obs(j), j = 0 .. O-1. The parameter words and the
-// observation elements are requested kChunk at a time, all of a chunk before the first is used
-// (one memory round per chunk instead of one dependent load per term), past the row's end
-// the last element again, so the requests are straight-line code; the sum itself runs in the
-// formula's order over the terms j < O alone.
-template <int kChunk, class Obs>
-SCG_SC_POLICY_HD float sc_policy_action(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs) {
-  const float* row = pv.params + sc_policy_param_index(pv, O, n, a, 0);
-  float z = row[static_cast<int64_t>(O) * pv.qstride];
-  for (int j0 = 0; j0 < O; j0 += kChunk) {
+// One row of a layer: z = bias; z = z + w[j] * in(j) for j = 0 .. L-1 ascending, for the L weight
+// words at row[j * qstride] and the bias word after them. The weight words and the inputs are
+// requested kChunk at a time, all of a chunk before the first is used (one memory round per
+// chunk instead of one dependent load per term), past the row's end the last element again,
+// so the requests are straight-line code; the sum itself runs in the formula's order over the
+// terms j < L alone. (The linear policy's action rows and both layers of scg_sc_mlp.h.)
+template <int kChunk, class In>
+SCG_SC_POLICY_HD float sc_policy_row_sum(const float* row, int64_t qstride, int L, const In& in) {
+  float z = row[static_cast<int64_t>(L) * qstride];
+  for (int j0 = 0; j0 < L; j0 += kChunk) {
     float wv[kChunk], ov[kChunk];
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
     for (int u = 0; u < kChunk; ++u) {
-      const int j = j0 + u < O ? j0 + u : O - 1;
-      wv[u] = row[static_cast<int64_t>(j) * pv.qstride];
-      ov[u] = obs(j);
+      const int j = j0 + u < L ? j0 + u : L - 1;
+      wv[u] = row[static_cast<int64_t>(j) * qstride];
+      ov[u] = in(j);
     }
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
     for (int u = 0; u < kChunk; ++u) {
       const float term = wv[u] * ov[u];
-      z = j0 + u < O ? z + term : z;
+      z = j0 + u < L ? z + term : z;
     }
   }
-  return sc_policy_clamp(z, pv.lo, pv.hi);
+  return z;
 }
 
-// What a closed-loop launch takes beside the step's launch arguments (scg_sc_nodes.hip).
-struct ScPolicyLaunch {
-  ScPolicyView pv;
+// Action a of env n from its observation obs(j), j = 0 .. O-1.
+template <int kChunk, class Obs>
+SCG_SC_POLICY_HD float sc_policy_action(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs) {
+  const float* row = pv.params + sc_policy_param_index(pv, O, n, a, 0);
+  return sc_policy_clamp(sc_policy_row_sum<kChunk>(row, pv.qstride, O, obs), pv.lo, pv.hi);
+}
+
+// What a closed-loop launch takes beside the step's launch arguments (scg_sc_nodes.hip), for
+// a policy read through View (ScPolicyView; scg_sc_mlp.h ScMlpView).
+template <class View>
+struct ScClosedLaunch {
+  View pv;
   void* obs_io;         // [N][O], obs dtype: read at the launch's first step, written at its last
   float* act_work;      // [N][A]: the launch's last action rows
   float* actions_out;   // [K][N][A] of this launch, or null
   double* reward_sum;   // [N]
   int32_t sum_add;      // 0: the launch stores its rewards' sum; else it adds to what is there
 };
+using ScPolicyLaunch = ScClosedLaunch<ScPolicyView>;
 
 }  // namespace scg

@@ -1,9 +1,10 @@
 // SupplyChain closed loop, host side and the small kernels (include/scgpu.h scg_sc_observe,
-// scg_sc_rollout_policy): the observation of a state as it stands, the action rows of a
-// linear policy from observation rows (csrc/scg_sc_policy.h: the one definition of the
-// formula), and the entry point that runs either the fused kernel (scg_sc_nodes.hip
-// sc_policy_rollout_nodes_kernel) or, for every other config, the action kernel and
-// scg_sc_step per step.
+// scg_sc_rollout_policy, scg_sc_rollout_mlp): the observation of a state as it stands, the
+// action rows of a linear policy or a one-hidden-layer ReLU policy from observation rows
+// (csrc/scg_sc_policy.h, csrc/scg_sc_mlp.h: the one definition of each formula), and the entry
+// points, one host body for both policies, which runs either the fused kernel (scg_sc_nodes.hip
+// sc_policy_rollout_nodes_kernel, sc_mlp_rollout_nodes_kernel) or, for every other case, the
+// action kernel and scg_sc_step per step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include "scg_supplychain_core.h"
 #include "scg_supplychain_args.h"
 #include "scg_sc_policy.h"
+#include "scg_sc_mlp.h"
 
 namespace scg {
 
@@ -21,6 +23,7 @@ ScArgs sc_host_args(const scg_sc_config* cfg, const scg_sc_state* st);
 int sc_rollout_chunk_steps();
 // scg_sc_nodes.hip
 int sc_launch_nodes_policy(const ScArgs& a, const ScPolicyLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s);
+int sc_launch_nodes_mlp(const ScArgs& a, const ScMlpLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s);
 
 // sc_reset_kernel's addressing without the reset: env n's observation at a.t of a.episode.
 __global__ __launch_bounds__(kScBlock) void sc_observe_kernel(const ScArgs a) {
@@ -61,37 +64,111 @@ __global__ __launch_bounds__(kPolicyActBlock) void sc_reward_sum_kernel(double* 
   sum[n] = s + r[n];
 }
 
-}  // namespace scg
-
-using namespace scg;
-
-extern "C" {
-
-int scg_sc_observe(const scg_sc_config* cfg, const scg_sc_state* st, void* obs, void* stream) {
-  if (int rc = sc_host_check(cfg, st)) return rc;
-  if (!obs) return fail(SCG_ERR_INVALID, "the obs buffer is required");
-  if (st->time_step < 0) return fail(SCG_ERR_NOT_RESET, "observe() before reset()");
-  ScArgs a = sc_host_args(cfg, st);
-  a.obs = obs;
-  a.t = st->time_step;
-  const dim3 grid(static_cast<unsigned>((st->n_envs + kScBlock - 1) / kScBlock));
-  hipLaunchKernelGGL(sc_observe_kernel, grid, dim3(kScBlock), 0, static_cast<hipStream_t>(stream), a);
-  return check_launch("sc_observe_kernel");
+// The MLP's action rows: thread l of a block is env blockIdx.x * 64 + l. It computes its env's H
+// hidden units from row n of obs [N][O] into its column of the block's hidden tile [H][64] in
+// dynamic LDS (lane fastest: conflict-free, and no register array that H = 64 would spill; 256 B
+// per unit, 16 KB at most), then its A
+// actions from that column into row n of out0 and, when given, out1 [N][A]. A thread reads and
+// writes its own column only: no barrier. Per-env parameter words are read as 256-byte rows.
+constexpr int kMlpActBlock = 64;
+constexpr int kMlpActChunk = 16;
+// (Four waves per SIMD: at most 128 VGPRs, as the node-parallel kernels.)
+__global__ __launch_bounds__(kMlpActBlock) __attribute__((amdgpu_waves_per_eu(4)))
+void sc_mlp_act_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1) {
+  extern __shared__ float hid_t[];  // [H][64]
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kMlpActBlock + threadIdx.x;
+  if (n >= N) return;
+  float* const hid = hid_t + threadIdx.x;
+  if (obs_f64) {
+    const double* row = static_cast<const double*>(obs) + n * O;
+    auto o = [&](int j) { return static_cast<float>(row[j]); };
+    for (int i = 0; i < mv.H; ++i) hid[i * kMlpActBlock] = sc_mlp_hidden<kMlpActChunk>(mv, O, n, i, o);
+  } else {
+    const float* row = static_cast<const float*>(obs) + n * O;
+    auto o = [&](int j) { return row[j]; };
+    for (int i = 0; i < mv.H; ++i) hid[i * kMlpActBlock] = sc_mlp_hidden<kMlpActChunk>(mv, O, n, i, o);
+  }
+  auto h = [&](int i) { return hid[i * kMlpActBlock]; };
+  for (int q = 0; q < A; ++q) {
+    const float act = sc_mlp_action<kMlpActChunk>(mv, O, n, q, h);
+    out0[n * A + q] = act;
+    if (out1) out1[n * A + q] = act;
+  }
 }
 
-int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_policy* policy,
-                          void* obs_io, float* act_work, float* actions_out, void* obs_out, double* rewards_out,
-                          double* reward_sum, void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
+// Whether hidden units fit the LDS the fused kernel has idle for them (a config scg_sc_prepare
+// has not derived an inbox for has none).
+bool sc_mlp_fits(const scg_sc_config* cfg, int32_t hidden) {
+  return cfg->inbox_size >= 0 && hidden <= sc_mlp_fused_hidden_max(cfg->inbox_size, cfg->n_nodes);
+}
+
+// What the closed loop's host body needs of a policy: its argument check, whether it fuses
+// beyond the linear condition, and its two launches.
+struct LinearHost {
+  const scg_sc_policy* pol;
+  int check() const {
+    if (!pol || !pol->params) return fail(SCG_ERR_INVALID, "a policy with device parameters is required");
+    if (!sc_policy_valid(pol->kind, pol->act_lo, pol->act_hi))
+      return fail(SCG_ERR_INVALID, "policy: kind must be SCG_SC_POLICY_LINEAR, act_lo <= act_hi, both finite");
+    return SCG_OK;
+  }
+  bool fits(const scg_sc_config*) const { return true; }
+  ScPolicyView view(int64_t N) const { return sc_policy_view(pol->params, pol->shared != 0, N, pol->act_lo, pol->act_hi); }
+  static int act(const ScPolicyView& pv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1,
+                 hipStream_t s) {
+    const dim3 grid(static_cast<unsigned>((N * A + kPolicyActBlock - 1) / kPolicyActBlock));
+    hipLaunchKernelGGL(sc_policy_act_kernel, grid, dim3(kPolicyActBlock), 0, s, pv, obs, obs_f64, N, A, O, out0, out1);
+    return check_launch("sc_policy_act_kernel");
+  }
+  static int fused(const ScArgs& a, const ScPolicyLaunch& p, int maxd, int W, int E, int K, hipStream_t s) {
+    return sc_launch_nodes_policy(a, p, maxd, W, E, K, s);
+  }
+};
+
+struct MlpHost {
+  const scg_sc_mlp* pol;
+  int check() const {
+    if (!pol || !pol->params) return fail(SCG_ERR_INVALID, "an mlp with device parameters is required");
+    if (!sc_mlp_valid(pol->hidden, pol->activation, pol->reserved, pol->act_lo, pol->act_hi))
+      return fail(SCG_ERR_INVALID,
+                  "mlp: hidden in 1..%d, activation SCG_SC_ACT_RELU, reserved 0, act_lo <= act_hi, both finite",
+                  SCG_SC_MLP_MAX_HIDDEN);
+    return SCG_OK;
+  }
+  bool fits(const scg_sc_config* cfg) const { return sc_mlp_fits(cfg, pol->hidden); }
+  ScMlpView view(int64_t N) const {
+    return sc_mlp_view(pol->params, pol->shared != 0, N, pol->hidden, pol->act_lo, pol->act_hi);
+  }
+  static int act(const ScMlpView& mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1,
+                 hipStream_t s) {
+    const dim3 grid(static_cast<unsigned>((N + kMlpActBlock - 1) / kMlpActBlock));
+    hipLaunchKernelGGL(sc_mlp_act_kernel, grid, dim3(kMlpActBlock), sizeof(float) * kMlpActBlock * mv.H, s, mv, obs, obs_f64, N, A, O, out0, out1);
+    return check_launch("sc_mlp_act_kernel");
+  }
+  static int fused(const ScArgs& a, const ScMlpLaunch& p, int maxd, int W, int E, int K, hipStream_t s) {
+    return sc_launch_nodes_mlp(a, p, maxd, W, E, K, s);
+  }
+};
+
+// The fused closed loop's condition: scg_sc_rollout's (a node-parallel config, no ledgers).
+bool sc_closed_fused(const scg_sc_config* cfg, const scg_sc_state* st) {
+  return cfg->kernel == SCG_SC_KERNEL_NODES && !st->ledger;
+}
+
+template <class Policy>
+int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const Policy& policy, void* obs_io,
+                      float* act_work, float* actions_out, void* obs_out, double* rewards_out, double* reward_sum,
+                      void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
   if (int rc = sc_host_check(cfg, st)) return rc;
-  if (!policy || !policy->params) return fail(SCG_ERR_INVALID, "a policy with device parameters is required");
-  if (!sc_policy_valid(policy->kind, policy->act_lo, policy->act_hi))
-    return fail(SCG_ERR_INVALID, "policy: kind must be SCG_SC_POLICY_LINEAR, act_lo <= act_hi, both finite");
+  if (int rc = policy.check()) return rc;
   if (!obs_io || !act_work || !reward_sum) return fail(SCG_ERR_INVALID, "obs_io/act_work/reward_sum buffers are required");
   if (n_steps < 0) return fail(SCG_ERR_INVALID, "rollout of %d steps", n_steps);
   if (flags & ~(SCG_BG_AUTORESET | SCG_SC_SERIAL)) return fail(SCG_ERR_INVALID, "unknown rollout flags");
-  const bool fused = cfg->kernel == SCG_SC_KERNEL_NODES && !st->ledger;
+  const bool fused = sc_closed_fused(cfg, st) && policy.fits(cfg);
   if (!fused && !rewards_out)
-    return fail(SCG_ERR_INVALID, "the per-step closed loop (every config but node-parallel without ledgers) needs rewards_out");
+    return fail(SCG_ERR_INVALID,
+                "the per-step closed loop (every case but node-parallel without ledgers, the policy in its LDS) needs "
+                "rewards_out");
   if (st->time_step < 0) return fail(SCG_ERR_NOT_RESET, "rollout_policy() before reset()");
   const int T = cfg->total_time_steps;
   if (st->time_step >= T) return fail(SCG_ERR_PAST_HORIZON, "rollout_policy() after the terminal step %d", T);
@@ -105,7 +182,7 @@ int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_
   const int64_t N = st->n_envs;
   const int A = cfg->n_actions, O = cfg->n_obs;
   const size_t obs_row = static_cast<size_t>(N) * O * (cfg->obs_f64 ? 8 : 4);
-  const ScPolicyView pv = sc_policy_view(policy->params, policy->shared != 0, N, policy->act_lo, policy->act_hi);
+  auto pv = policy.view(N);
   int32_t crossed = 0;
   if (n_done) *n_done = 0;
   if (n_steps == 0) {
@@ -114,15 +191,12 @@ int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_
   }
   if (!fused) {  // the action kernel and one step launch per step
     const uint32_t step_flags = flags & (SCG_BG_AUTORESET | SCG_SC_SERIAL);
-    const dim3 agrid(static_cast<unsigned>((N * A + kPolicyActBlock - 1) / kPolicyActBlock));
     const dim3 rgrid(static_cast<unsigned>((N + kPolicyActBlock - 1) / kPolicyActBlock));
     unsigned char* const oo = static_cast<unsigned char*>(obs_out);
     for (int32_t k = 0; k < n_steps; ++k) {
       const void* src = (k == 0 || !oo) ? obs_io : oo + obs_row * (k - 1);
       float* const arow = actions_out ? actions_out + static_cast<int64_t>(k) * N * A : nullptr;
-      hipLaunchKernelGGL(sc_policy_act_kernel, agrid, dim3(kPolicyActBlock), 0, s, pv, src, cfg->obs_f64, N, A, O, act_work,
-                         arow);
-      if (int rc = check_launch("sc_policy_act_kernel")) return rc;
+      if (int rc = Policy::act(pv, src, cfg->obs_f64, N, A, O, act_work, arow, s)) return rc;
       int32_t done = 0;
       double* const rrow = rewards_out + static_cast<int64_t>(k) * N;
       if (int rc = scg_sc_step(cfg, st, act_work, oo ? static_cast<void*>(oo + obs_row * k) : obs_io, rrow, terminal_obs,
@@ -149,9 +223,10 @@ int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_
     a.rew = rewards_out ? rewards_out + static_cast<int64_t>(k0) * N : nullptr;
     a.t = st->time_step + 1;
     a.flags = (reset ? 2 : 0) | ((flags & SCG_SC_SERIAL) ? 4 : 0);
-    const ScPolicyLaunch p{pv, obs_io, act_work, actions_out ? actions_out + static_cast<int64_t>(k0) * N * A : nullptr,
-                           reward_sum, k0 > 0 ? 1 : 0};
-    if (int rc = sc_launch_nodes_policy(a, p, maxd, cfg->group, cfg->inbox_size, kc, s)) return rc;
+    const ScClosedLaunch<decltype(pv)> p{pv, obs_io, act_work,
+                                         actions_out ? actions_out + static_cast<int64_t>(k0) * N * A : nullptr, reward_sum,
+                                         k0 > 0 ? 1 : 0};
+    if (int rc = Policy::fused(a, p, maxd, cfg->group, cfg->inbox_size, kc, s)) return rc;
     const int64_t end = static_cast<int64_t>(st->time_step) + kc;  // <= T without auto-reset
     if (reset) {
       crossed += static_cast<int32_t>(end / T);
@@ -164,6 +239,45 @@ int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_
   }
   if (n_done) *n_done = crossed;
   return SCG_OK;
+}
+
+}  // namespace scg
+
+using namespace scg;
+
+extern "C" {
+
+int scg_sc_observe(const scg_sc_config* cfg, const scg_sc_state* st, void* obs, void* stream) {
+  if (int rc = sc_host_check(cfg, st)) return rc;
+  if (!obs) return fail(SCG_ERR_INVALID, "the obs buffer is required");
+  if (st->time_step < 0) return fail(SCG_ERR_NOT_RESET, "observe() before reset()");
+  ScArgs a = sc_host_args(cfg, st);
+  a.obs = obs;
+  a.t = st->time_step;
+  const dim3 grid(static_cast<unsigned>((st->n_envs + kScBlock - 1) / kScBlock));
+  hipLaunchKernelGGL(sc_observe_kernel, grid, dim3(kScBlock), 0, static_cast<hipStream_t>(stream), a);
+  return check_launch("sc_observe_kernel");
+}
+
+int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_policy* policy,
+                          void* obs_io, float* act_work, float* actions_out, void* obs_out, double* rewards_out,
+                          double* reward_sum, void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
+  return sc_rollout_closed(cfg, st, n_steps, LinearHost{policy}, obs_io, act_work, actions_out, obs_out, rewards_out,
+                           reward_sum, terminal_obs, flags, n_done, stream);
+}
+
+int scg_sc_rollout_mlp(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_mlp* mlp, void* obs_io,
+                       float* act_work, float* actions_out, void* obs_out, double* rewards_out, double* reward_sum,
+                       void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
+  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, obs_io, act_work, actions_out, obs_out, rewards_out, reward_sum,
+                           terminal_obs, flags, n_done, stream);
+}
+
+int scg_sc_mlp_fused(const scg_sc_config* cfg, const scg_sc_state* st, int32_t hidden) {
+  if (int rc = sc_host_check(cfg, st)) return -rc;
+  if (hidden < 1 || hidden > SCG_SC_MLP_MAX_HIDDEN)
+    return -fail(SCG_ERR_INVALID, "mlp: hidden in 1..%d, got %d", SCG_SC_MLP_MAX_HIDDEN, hidden);
+  return sc_closed_fused(cfg, st) && sc_mlp_fits(cfg, hidden) ? 1 : 0;
 }
 
 }  // extern "C"

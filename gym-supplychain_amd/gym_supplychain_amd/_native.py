@@ -130,6 +130,17 @@ class ScPolicy(ctypes.Structure):
                 ("act_hi", ctypes.c_float), ("params", ctypes.c_void_p)]
 
 
+SC_ACT_RELU = 1  # scg_sc_mlp.activation
+SC_MLP_MAX_HIDDEN = 64
+
+
+class ScMlp(ctypes.Structure):
+    """scg_sc_mlp (include/scgpu.h): the one-hidden-layer ReLU policy of scg_sc_rollout_mlp."""
+    _fields_ = [("hidden", ctypes.c_int32), ("activation", ctypes.c_int32), ("shared", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("act_lo", ctypes.c_float), ("act_hi", ctypes.c_float),
+                ("params", ctypes.c_void_p)]
+
+
 class BgServerLine(ctypes.Structure):
     """scg_bg_server_line (include/scgpu.h): one slot's 64-byte request line."""
     _fields_ = [("req_seq", ctypes.c_uint32), ("cmd", ctypes.c_int32), ("wpack", ctypes.c_uint32),
@@ -298,6 +309,11 @@ SIGNATURES = {
                                              ctypes.POINTER(ScPolicy), ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_uint32, _i32p, ctypes.c_void_p]),
+    "scg_sc_rollout_mlp": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_int32,
+                                          ctypes.POINTER(ScMlp), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_uint32, _i32p, ctypes.c_void_p]),
+    "scg_sc_mlp_fused": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_int32]),
     "scg_sc_draw_tables": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_uint32,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_nodes_max_blocks": (ctypes.c_int, [ctypes.c_int32]),

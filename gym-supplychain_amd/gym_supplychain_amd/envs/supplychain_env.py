@@ -217,6 +217,25 @@ class ScPackedPolicy:
         self.params, self.shared, self.n_envs, self.n_actions, self.n_obs = params, shared, n_envs, n_actions, n_obs
 
 
+class ScPackedMlp:
+    """One-hidden-layer ReLU policy parameters as scg_sc_rollout_mlp reads them
+    (SupplyChainVecEnv.pack_mlp): `params` float32 on the env's device, [Q, N] (a policy per env)
+    or [Q] (`shared`), Q = H*(O+1) + A*(H+1)."""
+    __slots__ = ("params", "shared", "n_envs", "n_actions", "n_obs", "hidden")
+
+    def __init__(self, params, shared, n_envs, n_actions, n_obs, hidden):
+        self.params, self.shared, self.n_envs, self.n_actions, self.n_obs = params, shared, n_envs, n_actions, n_obs
+        self.hidden = hidden
+
+
+def pack_mlp_words(w1, b1, w2, b2):
+    """float32 tensors W1 [..., H, O], b1 [..., H], W2 [..., A, H], b2 [..., A] with the same
+    leading shape, () or (N,), to the words of scg_sc_mlp: [Q] or [Q, N] (env fastest)."""
+    words = torch.cat([torch.cat([w1, b1.unsqueeze(-1)], dim=-1).flatten(-2),
+                       torch.cat([w2, b2.unsqueeze(-1)], dim=-1).flatten(-2)], dim=-1)
+    return words.contiguous() if words.dim() == 1 else words.t().contiguous()
+
+
 class ScPolicyRollout:
     """What SupplyChainVecEnv.rollout_policy returns: `reward_sum` float64 [N], `last_obs`
     [N, n_obs] (the env's own buffer: clone() to keep it), `dones` CPU bool [K], and `actions`
@@ -235,6 +254,7 @@ class SupplyChainVecEnv:
     step(actions float32 [N, n_actions] in [-1, 1]) -> (obs, reward float64 [N], done bool [N], info)
     rollout(actions float32 [K, N, n_actions]) -> (obs [K, N, n_obs], rewards [K, N], dones [K]): K steps, one call
     rollout_policy(weights, bias, n_steps) -> ScPolicyRollout: K steps with a linear policy's actions computed on the device
+    rollout_policy(pack_mlp(w1, b1, w2, b2), None, n_steps): the same with a one-hidden-layer ReLU policy
     observe() -> obs [N, n_obs]: the current observation, whatever call left the state
 
     Returned tensors are this env's output buffers (clone() to keep them). With
@@ -566,6 +586,38 @@ class SupplyChainVecEnv:
         words = torch.cat([w, b.expand(N, A).unsqueeze(2)], dim=2).reshape(N, A * (O + 1))
         return ScPackedPolicy(words.t().contiguous(), False, N, A, O)
 
+    def pack_mlp(self, w1, b1, w2, b2):
+        """One-hidden-layer ReLU policy parameters in the layout scg_sc_rollout_mlp reads, float32
+        on this env's device. Per env: w1 [N, H, O], b1 [N, H] or [H], w2 [N, A, H], b2 [N, A] or
+        [A], packed [Q, N] env fastest; shared: w1 [H, O], b1 [H], w2 [A, H], b2 [A], packed [Q].
+        Q = H*(O+1) + A*(H+1): word i*(O+1)+j is w1[i][j] (j < O) or b1[i] (j == O), word
+        H*(O+1) + a*(H+1) + i is w2[a][i] (i < H) or b2[a] (i == H). H comes from the shapes
+        (1..64). Values must be exactly representable as float32. ValueError otherwise, and
+        when per-env and shared shapes are mixed."""
+        N, A, O = self.n_envs, self.n_actions, self.n_obs
+        shape = tuple(w1.shape) if hasattr(w1, "shape") else tuple(np.shape(w1))
+        if len(shape) not in (2, 3) or shape[-1] != O or (len(shape) == 3 and shape[0] != N):
+            raise ValueError(f"w1 must have shape [{N}, H, {O}] or [H, {O}], got {list(shape)}")
+        H, shared = int(shape[-2]), len(shape) == 2
+        if not 1 <= H <= nat.SC_MLP_MAX_HIDDEN:
+            raise ValueError(f"the hidden width must be in 1..{nat.SC_MLP_MAX_HIDDEN}, got {H}")
+        w1 = self._exact_f32("w1", w1, ((H, O),) if shared else ((N, H, O),))
+        b1 = self._exact_f32("b1", b1, ((H,),) if shared else ((N, H), (H,)))
+        w2 = self._exact_f32("w2", w2, ((A, H),) if shared else ((N, A, H),))
+        b2 = self._exact_f32("b2", b2, ((A,),) if shared else ((N, A), (A,)))
+        if not shared:
+            b1, b2 = b1.expand(N, H), b2.expand(N, A)
+        return ScPackedMlp(pack_mlp_words(w1, b1, w2, b2), shared, N, A, O, H)
+
+    def mlp_fused(self, hidden):
+        """Whether rollout_policy() of an MLP of that hidden width runs in one launch on this
+        env (scg_sc_mlp_fused): the node-parallel kernel without build_info, and the hidden
+        units fitting the LDS its block has idle. Otherwise it runs per step."""
+        rc = nat.lib.scg_sc_mlp_fused(self._cfg_ref, self._st_ref, int(hidden))
+        if rc < 0:
+            nat.check(-rc)
+        return bool(rc)
+
     def rollout_policy(self, weights, bias=None, n_steps=None, clip=None, return_actions=False, return_obs=False,
                        return_rewards=False):
         """n_steps steps with every env's action row computed on the device from the
@@ -585,9 +637,17 @@ class SupplyChainVecEnv:
 
         On the node-parallel kernel without build_info the steps run in one launch (per 1024),
         the product going from the step's observation tile to the next step's action tile in
-        LDS; every other kernel runs an action kernel and a step per step."""
+        LDS; every other kernel runs an action kernel and a step per step.
+
+        weights may also be a pack_mlp() result (bias None): the actions are then those of a
+        one-hidden-layer ReLU policy, float32 in the same manner,
+
+            h[i] = b1[i];  for j in range(n_obs): h[i] = h[i] + w1[i][j] * o[j];  h[i] = h[i] if h[i] > 0 else +0.0
+            z[a] = b2[a];  for i in range(H): z[a] = z[a] + w2[a][i] * h[i]
+
+        clipped as above; mlp_fused(H) tells whether the steps run in one launch."""
         N, A, O = self.n_envs, self.n_actions, self.n_obs
-        if isinstance(weights, ScPackedPolicy):
+        if isinstance(weights, (ScPackedPolicy, ScPackedMlp)):
             if bias is not None:
                 raise ValueError("a packed policy carries its bias")
             packed = weights
@@ -607,7 +667,8 @@ class SupplyChainVecEnv:
         if getattr(self, "_pol_obs", None) is None:  # the call's own buffers, kept for the next
             self._pol_obs = torch.empty((N, O), dtype=self.obs_dtype, device=dev)
             self._pol_act = torch.empty((N, A), dtype=torch.float32, device=dev)
-        fused = self.kernel == "nodes" and not self.build_info
+        mlp = isinstance(packed, ScPackedMlp)
+        fused = self.mlp_fused(packed.hidden) if mlp else self.kernel == "nodes" and not self.build_info
         rewards = torch.empty((K, N), dtype=torch.float64, device=dev) if (return_rewards or not fused) else None
         res = ScPolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), self._pol_obs, None,
                               torch.empty((K, N, A), dtype=torch.float32, device=dev) if return_actions else None,
@@ -616,13 +677,19 @@ class SupplyChainVecEnv:
         t0, T = self._st.time_step, self.spec.total_time_steps
         if t0 >= 0:  # (before a reset the library refuses below)
             self.observe(self._pol_obs)
-        pol = nat.ScPolicy(nat.SC_POLICY_LINEAR, int(packed.shared), float(lo32), float(hi32), packed.params.data_ptr())
+        if mlp:
+            pol = nat.ScMlp(packed.hidden, nat.SC_ACT_RELU, int(packed.shared), 0, float(lo32), float(hi32),
+                            packed.params.data_ptr())
+            entry = nat.lib.scg_sc_rollout_mlp
+        else:
+            pol = nat.ScPolicy(nat.SC_POLICY_LINEAR, int(packed.shared), float(lo32), float(hi32),
+                               packed.params.data_ptr())
+            entry = nat.lib.scg_sc_rollout_policy
         n_done = ctypes.c_int32(0)
-        nat.check(nat.lib.scg_sc_rollout_policy(self._cfg_ref, self._st_ref, int(n_steps), ctypes.byref(pol),
-                                                self._pol_obs.data_ptr(), self._pol_act.data_ptr(),
-                                                nat.ptr(res.actions), nat.ptr(res.obs), nat.ptr(rewards),
-                                                res.reward_sum.data_ptr(), self._term_ptr, self._flags,
-                                                ctypes.byref(n_done), self._stream()))
+        nat.check(entry(self._cfg_ref, self._st_ref, int(n_steps), ctypes.byref(pol),
+                        self._pol_obs.data_ptr(), self._pol_act.data_ptr(), nat.ptr(res.actions), nat.ptr(res.obs),
+                        nat.ptr(rewards), res.reward_sum.data_ptr(), self._term_ptr, self._flags, ctypes.byref(n_done),
+                        self._stream()))
         res.dones = (torch.arange(t0 + 1, t0 + K + 1) % T) == 0
         if n_done.value:
             self.check_errors()

@@ -48,7 +48,9 @@ extern "C" {
  *   the testing hook scg_sc_rollout_chunk; also scg_bg_rollout_policy (scg_bg_policy: the
  *   closed-loop BeerGame rollout with a per-env linear policy), an added entry point; also
  *   scg_sc_observe and scg_sc_rollout_policy (scg_sc_policy: the closed-loop SupplyChain
- *   rollout with a linear policy, per env or shared), added entry points. */
+ *   rollout with a linear policy, per env or shared), added entry points; also
+ *   scg_sc_rollout_mlp and scg_sc_mlp_fused (scg_sc_mlp: the same closed loop with a
+ *   one-hidden-layer ReLU policy), added entry points. */
 #define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
@@ -696,6 +698,46 @@ SCG_API int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, in
                                   const scg_sc_policy* policy, void* obs_io, float* act_work, float* actions_out,
                                   void* obs_out, double* rewards_out, double* reward_sum, void* terminal_obs,
                                   uint32_t flags, int32_t* n_done, void* stream);
+
+/*
+ * The same closed loop with a one-hidden-layer ReLU policy of hidden width H. For the
+ * observation o[0..O) as float32 (as above) and float32 parameters W1[H][O], b1[H], W2[A][H],
+ * b2[A]:
+ *   h_i = b1_i;  for j = 0 .. O-1 ascending:  h_i = h_i + W1[i][j] * o_j;   h_i = (h_i > 0) ? h_i : +0.0f
+ *   z_a = b2_a;  for i = 0 .. H-1 ascending:  z_a = z_a + W2[a][i] * h_i
+ *   act_a = !(z_a >= act_lo) ? act_lo : (z_a > act_hi ? act_hi : z_a)
+ * every multiply and add rounded to float32 on its own (no FMA); a NaN or -0 pre-activation
+ * gives +0, a NaN z gives act_lo (csrc/scg_sc_mlp.h is the one definition, host and device).
+ * A policy is Q = H*(O+1) + A*(H+1) words: word i*(O+1)+j is W1[i][j] for j < O and b1[i] for
+ * j == O; word H*(O+1) + a*(H+1) + i is W2[a][i] for i < H and b2[a] for i == H. params is
+ * DEVICE float32 [Q][N], env fastest (shared == 0), or [Q] (shared != 0).
+ *
+ * Buffers, flags, contract and error codes are scg_sc_rollout_policy's; SCG_ERR_INVALID also
+ * for hidden outside 1..SCG_SC_MLP_MAX_HIDDEN, an unknown activation and reserved != 0.
+ * Fused under the linear policy's condition when also H <= 2 * (inbox_size + n_nodes): the
+ * hidden units of a block's 64 envs then live in LDS the step leaves idle between its last
+ * barrier and the next step's first (the shipment inbox and node cost rows), so the block
+ * needs no more LDS than the linear closed loop's. Every other case (it is not an error) runs
+ * an action kernel and scg_sc_step per step and needs rewards_out. scg_sc_mlp_fused tells
+ * which: 1 fused, 0 per step, -SCG_ERR_INVALID for a bad config, state or hidden; host only,
+ * no HIP call.
+ */
+#define SCG_SC_MLP_MAX_HIDDEN 64
+#define SCG_SC_ACT_RELU 1
+typedef struct scg_sc_mlp {
+  int32_t hidden;        /* 1 .. SCG_SC_MLP_MAX_HIDDEN */
+  int32_t activation;    /* SCG_SC_ACT_RELU */
+  int32_t shared;        /* 0: params per env [Q][N]; else one policy [Q] */
+  int32_t reserved;      /* 0 */
+  float act_lo, act_hi;  /* finite, act_lo <= act_hi */
+  const float* params;   /* DEVICE float32 */
+} scg_sc_mlp;            /* 32 bytes, params at 24 */
+
+SCG_API int scg_sc_rollout_mlp(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_mlp* mlp,
+                               void* obs_io, float* act_work, float* actions_out, void* obs_out,
+                               double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags,
+                               int32_t* n_done, void* stream);
+SCG_API int scg_sc_mlp_fused(const scg_sc_config* cfg, const scg_sc_state* st, int32_t hidden);
 
 /* The per-episode tables scg_sc_step draws (for tests): demand DEVICE int32
  * [N][T+1][R][P], leadtimes DEVICE int32 [N][T][n_leadtimes] (NULL when deterministic). */
