@@ -10,6 +10,8 @@
 // float32 first), and hidden width H. Every multiply and every add is rounded to float32 on
 // its own (the units that include this are built with -ffp-contract=off), as NumPy computes
 // the same loops; a NaN or -0 pre-activation gives +0, a NaN z gives lo (sc_policy_clamp).
+// Sampled (scg_sc_rollout_sampled): act_a is the clamp of u_a = z_a + (std_a * eps), as
+// scg_sc_policy.h states it for both policies.
 // Each layer's row is the linear policy's row (scg_sc_policy.h sc_policy_row_sum: L weight
 // words, then the bias) under another epilogue.
 //
@@ -68,6 +70,16 @@ template <int kChunk, class Hid>
 SCG_SC_POLICY_HD float sc_mlp_action(const ScMlpView& mv, int O, int64_t n, int a, const Hid& hid) {
   const float* row = mv.params + sc_mlp_param_index(mv, O, n, 1, a, 0);
   return sc_policy_clamp(sc_policy_row_sum<kChunk>(row, mv.qstride, mv.H, hid), mv.lo, mv.hi);
+}
+
+// The same action sampled (scg_sc_policy.h sc_policy_sample): u (stored to *u_out) and its clamp.
+template <int kChunk, class Hid>
+SCG_SC_POLICY_HD float sc_mlp_action_sampled(const ScMlpView& mv, int O, int64_t n, int a, const Hid& hid, float std, float eps,
+                                             float* u_out) {
+  const float* row = mv.params + sc_mlp_param_index(mv, O, n, 1, a, 0);
+  const float u = sc_policy_sample(sc_policy_row_sum<kChunk>(row, mv.qstride, mv.H, hid), std, eps);
+  *u_out = u;
+  return sc_policy_clamp(u, mv.lo, mv.hi);
 }
 
 using ScMlpLaunch = ScClosedLaunch<ScMlpView>;

@@ -206,14 +206,22 @@ struct NodesRolloutStep {
 // previous step left (kPolicy: the parts of sc_nodes_tile that differ), by the policy Launch
 // carries (ScPolicyLaunch: linear; ScMlpLaunch: one hidden layer). Every output is optional;
 // first() / last(): the tile's first and last step in the launch, where obs_io is read and
-// obs_io, act_work and reward_sum are written.
+// obs_io, act_work and reward_sum are written. A sampled launch (ScSampledLaunch, kSampled)
+// adds the caller's noise to every action before its clamp: noise(x, n, row) is env n's part of
+// noise row `row` of the launch, the row of the step the actions are computed for.
+struct NodesNoise {
+  const float* std;  // [A]
+  const float* eps;  // the env's noise row [A]
+  float* out;        // the env's row of samples_out [A], or null
+};
 template <class Launch>
 struct NodesClosedStep {
   static constexpr bool kKeepsState = true;
   static constexpr bool kStreamOut = true;
   static constexpr bool kObsOptional = true;
   static constexpr bool kPolicy = true;
-  static constexpr bool kMlp = std::is_same<Launch, ScMlpLaunch>::value;
+  static constexpr bool kMlp = std::is_same<decltype(Launch::pv), ScMlpView>::value;
+  static constexpr bool kSampled = Launch::kSampled;
   const Launch& p;
   int32_t t_, flags_;
   uint32_t episode_;
@@ -238,6 +246,10 @@ struct NodesClosedStep {
   __device__ __forceinline__ bool write_back() const { return write_back_; }
   __device__ __forceinline__ bool first() const { return k_ == 0; }
   __device__ __forceinline__ bool last() const { return last_; }
+  __device__ __forceinline__ NodesNoise noise(const ScArgs& x, int64_t n, int row) const {
+    const int64_t at = sc_sample_index(x.n, x.c.A, row, n, 0);
+    return NodesNoise{p.smp.std, p.smp.noise + at, p.smp.samples ? p.smp.samples + at : nullptr};
+  }
 };
 using NodesPolicyStep = NodesClosedStep<ScPolicyLaunch>;
 using NodesMlpStep = NodesClosedStep<ScMlpLaunch>;
@@ -272,6 +284,67 @@ __device__ __forceinline__ void sc_nodes_mlp_act(const ScMlpView& mv, int A, int
   if (live) {
     auto h = [&](int i) { return hid[i * 64]; };
     for (int q = w; q < A; q += W) arow[q] = sc_mlp_action<kNodesPolicyChunk>(mv, O, n, q, h);
+  }
+}
+
+// The sampled closed loop (kSampled steps): the same products with the caller's noise added
+// before the clamp (scg_sc_policy.h sc_policy_sample). The thread that computes action q of its
+// env reads the env's noise element q itself and, where samples are asked for, writes u to the
+// same index: per-thread strided accesses (lane stride A floats), no LDS and no barrier, and
+// samples_out may be the noise buffer. The block's threads together read every byte of the
+// tile's contiguous span [64][A], so each cache line is fetched from HBM once. The noise does
+// not depend on the step before it: a thread requests its first kNodesNoiseAhead elements ahead
+// of the first parameter words (the MLP: ahead of the hidden layer's), in the round the
+// deterministic loop already waits for; an env with more than kNodesNoiseAhead * W actions
+// reads the rest as it comes to them. (Requesting them a phase or a whole step earlier, or
+// reading the span coalesced through the action tile, measured no faster: DESIGN §6.13.)
+constexpr int kNodesNoiseAhead = 2;
+__device__ __forceinline__ void sc_nodes_noise_request(const NodesNoise& nz, int A, int w, int W, float (&ev)[kNodesNoiseAhead]) {
+#pragma unroll
+  for (int u = 0; u < kNodesNoiseAhead; ++u) ev[u] = w + u * W < A ? nz.eps[w + u * W] : 0.0f;
+}
+// Actions w, w + W, ... of the lane's env: act(q, std, eps, &u) is the policy's sampled action q.
+template <class Act>
+__device__ __forceinline__ void sc_nodes_sampled_actions(const NodesNoise& nz, int A, int w, int W,
+                                                         const float (&ev)[kNodesNoiseAhead], float* arow, const Act& act) {
+  auto one = [&](int q, float eps) {
+    float u;
+    arow[q] = act(q, nz.std[q], eps, &u);
+    if (nz.out) __hip_atomic_store(&nz.out[q], u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+#pragma unroll
+  for (int u = 0; u < kNodesNoiseAhead; ++u)
+    if (w + u * W < A) one(w + u * W, ev[u]);
+  for (int q = w + kNodesNoiseAhead * W; q < A; q += W) one(q, nz.eps[q]);
+}
+
+template <class ObsT>
+__device__ __forceinline__ void sc_nodes_policy_act_sampled(const ScPolicyView& pv, int A, int O, int64_t n, int w, int W,
+                                                            const ObsT* orow, float* arow, const NodesNoise& nz) {
+  float ev[kNodesNoiseAhead];
+  sc_nodes_noise_request(nz, A, w, W, ev);
+  auto o = [&](int j) { return static_cast<float>(orow[j]); };
+  sc_nodes_sampled_actions(nz, A, w, W, ev, arow, [&](int q, float sd, float eps, float* u) {
+    return sc_policy_action_sampled<kNodesPolicyChunk>(pv, O, n, q, o, sd, eps, u);
+  });
+}
+
+// (sc_nodes_mlp_act's two stages and barrier; every thread of the block calls it.)
+template <class ObsT>
+__device__ __forceinline__ void sc_nodes_mlp_act_sampled(const ScMlpView& mv, int A, int O, int64_t n, bool live, int w, int W,
+                                                         const ObsT* orow, float* arow, float* hid, const NodesNoise& nz) {
+  float ev[kNodesNoiseAhead];
+  if (live) {
+    sc_nodes_noise_request(nz, A, w, W, ev);
+    auto o = [&](int j) { return static_cast<float>(orow[j]); };
+    for (int i = w; i < mv.H; i += W) hid[i * 64] = sc_mlp_hidden<kNodesPolicyChunk>(mv, O, n, i, o);
+  }
+  __syncthreads();
+  if (live) {
+    auto h = [&](int i) { return hid[i * 64]; };
+    sc_nodes_sampled_actions(nz, A, w, W, ev, arow, [&](int q, float sd, float eps, float* u) {
+      return sc_mlp_action_sampled<kNodesPolicyChunk>(mv, O, n, q, h, sd, eps, u);
+    });
   }
 }
 
@@ -341,7 +414,14 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw.next()) obs_t[tw.r * Op + tw.k] = src[q];
       if (w == 0 && live) rsum[lane] = sp.p.sum_add ? sp.p.reward_sum[n] : 0.0;
       __syncthreads();
-      if constexpr (Step::kMlp) {
+      if constexpr (Step::kSampled) {  // the noise row of this step: the launch's first
+        if constexpr (Step::kMlp) {
+          sc_nodes_mlp_act_sampled(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap,
+                                   reinterpret_cast<float*>(ibval) + lane, sp.noise(a, n, 0));
+        } else if (live) {
+          sc_nodes_policy_act_sampled(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap, sp.noise(a, n, 0));
+        }
+      } else if constexpr (Step::kMlp) {
         sc_nodes_mlp_act(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap,
                          reinterpret_cast<float*>(ibval) + lane);
       } else if (live) {
@@ -576,6 +656,13 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw2.next())
         __hip_atomic_store(&dst[q], obs_t[tw2.r * Op + tw2.k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (w == 0 && live) sp.p.reward_sum[n] = rsum[lane];
+    } else if constexpr (Step::kSampled) {  // the next step's noise row (this is not the launch's last step)
+      if constexpr (Step::kMlp) {
+        sc_nodes_mlp_act_sampled(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap,
+                                 reinterpret_cast<float*>(ibval) + lane, sp.noise(a, n, sp.k_ + 1));
+      } else if (live) {
+        sc_nodes_policy_act_sampled(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap, sp.noise(a, n, sp.k_ + 1));
+      }
     } else if constexpr (Step::kMlp) {
       sc_nodes_mlp_act(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap, reinterpret_cast<float*>(ibval) + lane);
     } else if (live) {
@@ -808,6 +895,56 @@ void sc_mlp_rollout_nodes_kernel(const ScMlpKArgs k_arg, int W, int E, int K) {
       const bool autoreset = terminal && (a.flags & 2);
       const bool last = k == K - 1;
       NodesMlpStep sp{ka.p};
+      sp.t_ = t;
+      sp.flags_ = (terminal ? 1 : 0) | (autoreset ? 2 : 0) | (a.flags & 4);
+      sp.episode_ = episode;
+      sp.k_ = k;
+      sp.keep_ = keep;
+      sp.write_back_ = last || autoreset;
+      sp.last_ = last;
+      sc_nodes_tile<MAXD, F64, false>(a, tile, lane, w, W, E, sp);
+      keep = !autoreset;
+      if (autoreset) {
+        t = 1;
+        ++episode;
+      } else {
+        ++t;
+      }
+    }
+  }
+}
+
+// The sampled closed loop (scg_sc_rollout_sampled) of either policy: the same loops under
+// NodesClosedStep<ScSampledLaunch<...>>, in kernels of their own, so the deterministic kernels
+// above keep their code.
+template <class Launch>
+struct ScSampledKArgs {
+  ScArgs a;
+  Launch p;
+};
+
+template <int MAXD, bool F64, class Launch>
+__global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(kNodesWavesPerEu)))
+void sc_sampled_rollout_nodes_kernel(const ScSampledKArgs<Launch> k_arg, int W, int E, int K) {
+  const int lane0 = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t n_tiles = (k_arg.a.n + 63) / 64;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    int32_t t = k_arg.a.t;
+    uint32_t episode = k_arg.a.episode;
+    bool keep = false;
+    for (int k = 0; k < K; ++k) {
+      // lane and launch arguments opaque per step, as in the rollout kernel
+      int lane;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane0));
+      typedef const __attribute__((address_space(4))) ScSampledKArgs<Launch>* KArgPtr;
+      KArgPtr ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(ap));
+      const ScSampledKArgs<Launch>& ka = *(const ScSampledKArgs<Launch>*)ap;
+      const ScArgs& a = ka.a;
+      const bool terminal = t == a.c.T;
+      const bool autoreset = terminal && (a.flags & 2);
+      const bool last = k == K - 1;
+      NodesClosedStep<Launch> sp{ka.p};
       sp.t_ = t;
       sp.flags_ = (terminal ? 1 : 0) | (autoreset ? 2 : 0) | (a.flags & 4);
       sp.episode_ = episode;
@@ -1122,15 +1259,21 @@ int sc_launch_nodes_closed_d(const ScArgs& a, const Launch& p, int W, int E, int
 
 template <class Launch>
 int sc_launch_nodes_closed(const ScArgs& a, const Launch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
-  constexpr bool kMlp = std::is_same<Launch, ScMlpLaunch>::value;
+  constexpr bool kMlp = std::is_same<decltype(Launch::pv), ScMlpView>::value;
   if (W < 1 || W > kNodesMaxWaves) return fail(SCG_ERR_INVALID, "closed-loop rollout: %d waves per block", W);
   if (a.led_v) return fail(SCG_ERR_INVALID, "closed-loop rollout: no ledgers");
   if (K < 1) return fail(SCG_ERR_INVALID, "closed-loop rollout: steps");
   int rc = SCG_OK;
   const bool found = sc_dispatch_maxd<8>(maxd_bucket, [&](auto d) {
     constexpr int D = decltype(d)::value;
-    constexpr const char* name = kMlp ? "sc_mlp_rollout_nodes_kernel" : "sc_policy_rollout_nodes_kernel";
-    if constexpr (kMlp) {
+    constexpr const char* name = Launch::kSampled ? "sc_sampled_rollout_nodes_kernel"
+                                 : kMlp           ? "sc_mlp_rollout_nodes_kernel"
+                                                  : "sc_policy_rollout_nodes_kernel";
+    if constexpr (Launch::kSampled) {
+      using KArgs = ScSampledKArgs<Launch>;
+      rc = a.obs_f64 ? sc_launch_nodes_closed_d<&sc_sampled_rollout_nodes_kernel<D, true, Launch>, true, KArgs>(a, p, W, E, K, s, name)
+                     : sc_launch_nodes_closed_d<&sc_sampled_rollout_nodes_kernel<D, false, Launch>, false, KArgs>(a, p, W, E, K, s, name);
+    } else if constexpr (kMlp) {
       rc = a.obs_f64 ? sc_launch_nodes_closed_d<&sc_mlp_rollout_nodes_kernel<D, true>, true, ScMlpKArgs>(a, p, W, E, K, s, name)
                      : sc_launch_nodes_closed_d<&sc_mlp_rollout_nodes_kernel<D, false>, false, ScMlpKArgs>(a, p, W, E, K, s, name);
     } else {
@@ -1150,6 +1293,21 @@ int sc_launch_nodes_policy(const ScArgs& a, const ScPolicyLaunch& p, int maxd_bu
 // The hidden tile lies over the inbox values and cost rows of the block's LDS (sc_nodes_tile):
 // a wider one would run into the stocks behind them.
 int sc_launch_nodes_mlp(const ScArgs& a, const ScMlpLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
+  if (p.pv.H < 1 || p.pv.H > sc_mlp_fused_hidden_max(E, a.c.n_nodes))
+    return fail(SCG_ERR_INVALID, "closed-loop rollout: %d hidden units do not fit the block's idle LDS", p.pv.H);
+  return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);
+}
+
+// The sampled launches of both policies (sc_sampled_rollout_nodes_kernel).
+int sc_launch_nodes_policy_sampled(const ScArgs& a, const ScSampledLaunch<ScPolicyView>& p, int maxd_bucket, int W, int E, int K,
+                                   hipStream_t s) {
+  if (!p.smp.std || !p.smp.noise) return fail(SCG_ERR_INVALID, "sampled closed-loop rollout: std and noise are required");
+  return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);
+}
+
+int sc_launch_nodes_mlp_sampled(const ScArgs& a, const ScSampledLaunch<ScMlpView>& p, int maxd_bucket, int W, int E, int K,
+                                hipStream_t s) {
+  if (!p.smp.std || !p.smp.noise) return fail(SCG_ERR_INVALID, "sampled closed-loop rollout: std and noise are required");
   if (p.pv.H < 1 || p.pv.H > sc_mlp_fused_hidden_max(E, a.c.n_nodes))
     return fail(SCG_ERR_INVALID, "closed-loop rollout: %d hidden units do not fit the block's idle LDS", p.pv.H);
   return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);

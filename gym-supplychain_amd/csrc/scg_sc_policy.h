@@ -15,6 +15,15 @@
 // 256-byte row; shared they are float32 [A*(O+1)], one policy for every env. The same code
 // reads both through two strides: word q of env n is params[q * qstride + n * nstride], with
 // (qstride, nstride) = (N, 1) per env and (1, 0) shared.
+//
+// Sampled actions (scg_sc_rollout_sampled, scg_sc_sampling), for this policy and for the MLP of
+// scg_sc_mlp.h alike: with z_a as above, a standard deviation std_a and the caller's noise eps,
+//
+//   u_a   = z_a + (std_a * eps[k][n][a])      the product rounded to float32, then the sum
+//   act_a = !(u_a >= lo) ? lo : (u_a > hi ? hi : u_a)
+//
+// k the step's index in the call; a NaN u (a NaN z, 0 * inf) gives lo. sc_policy_sample is the
+// one definition of u.
 #pragma once
 
 #include <cstdint>
@@ -86,6 +95,25 @@ SCG_SC_POLICY_HD float sc_policy_row_sum(const float* row, int64_t qstride, int 
   return z;
 }
 
+// The sample u of an action whose formula gave z before its clamp.
+SCG_SC_POLICY_HD float sc_policy_sample(float z, float std, float eps) {
+  const float d = std * eps;
+  return z + d;
+}
+
+// The noise of one launch (or, on the host side, one call) of a sampled closed loop: std [A],
+// the noise rows [K][N][A] from the launch's first step on and, when asked for, the rows the
+// samples go to (which may be the noise rows themselves: an element is read, then written, by
+// one thread).
+struct ScSampleView {
+  const float* std;
+  const float* noise;
+  float* samples;  // or null
+};
+
+// Element (k, n, a) of the noise and sample rows.
+SCG_SC_POLICY_HD int64_t sc_sample_index(int64_t N, int A, int64_t k, int64_t n, int a) { return (k * N + n) * A + a; }
+
 // Action a of env n from its observation obs(j), j = 0 .. O-1.
 template <int kChunk, class Obs>
 SCG_SC_POLICY_HD float sc_policy_action(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs) {
@@ -93,10 +121,21 @@ SCG_SC_POLICY_HD float sc_policy_action(const ScPolicyView& pv, int O, int64_t n
   return sc_policy_clamp(sc_policy_row_sum<kChunk>(row, pv.qstride, O, obs), pv.lo, pv.hi);
 }
 
+// The same action sampled: u (stored to *u_out) and its clamp.
+template <int kChunk, class Obs>
+SCG_SC_POLICY_HD float sc_policy_action_sampled(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs, float std,
+                                                float eps, float* u_out) {
+  const float* row = pv.params + sc_policy_param_index(pv, O, n, a, 0);
+  const float u = sc_policy_sample(sc_policy_row_sum<kChunk>(row, pv.qstride, O, obs), std, eps);
+  *u_out = u;
+  return sc_policy_clamp(u, pv.lo, pv.hi);
+}
+
 // What a closed-loop launch takes beside the step's launch arguments (scg_sc_nodes.hip), for
 // a policy read through View (ScPolicyView; scg_sc_mlp.h ScMlpView).
 template <class View>
 struct ScClosedLaunch {
+  static constexpr bool kSampled = false;
   View pv;
   void* obs_io;         // [N][O], obs dtype: read at the launch's first step, written at its last
   float* act_work;      // [N][A]: the launch's last action rows
@@ -105,5 +144,18 @@ struct ScClosedLaunch {
   int32_t sum_add;      // 0: the launch stores its rewards' sum; else it adds to what is there
 };
 using ScPolicyLaunch = ScClosedLaunch<ScPolicyView>;
+
+// A sampled closed-loop launch: the same, and the launch's noise.
+template <class View>
+struct ScSampledLaunch {
+  static constexpr bool kSampled = true;
+  View pv;
+  void* obs_io;
+  float* act_work;
+  float* actions_out;
+  double* reward_sum;
+  int32_t sum_add;
+  ScSampleView smp;
+};
 
 }  // namespace scg

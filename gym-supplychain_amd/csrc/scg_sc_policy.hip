@@ -1,6 +1,7 @@
 // SupplyChain closed loop, host side and the small kernels (include/scgpu.h scg_sc_observe,
-// scg_sc_rollout_policy, scg_sc_rollout_mlp): the observation of a state as it stands, the
-// action rows of a linear policy or a one-hidden-layer ReLU policy from observation rows
+// scg_sc_rollout_policy, scg_sc_rollout_mlp, scg_sc_rollout_sampled): the observation of a state
+// as it stands, the action rows of a linear policy or a one-hidden-layer ReLU policy from
+// observation rows, deterministic or with the caller's noise added before the clamp
 // (csrc/scg_sc_policy.h, csrc/scg_sc_mlp.h: the one definition of each formula), and the entry
 // points, one host body for both policies, which runs either the fused kernel (scg_sc_nodes.hip
 // sc_policy_rollout_nodes_kernel, sc_mlp_rollout_nodes_kernel) or, for every other case, the
@@ -24,6 +25,10 @@ int sc_rollout_chunk_steps();
 // scg_sc_nodes.hip
 int sc_launch_nodes_policy(const ScArgs& a, const ScPolicyLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s);
 int sc_launch_nodes_mlp(const ScArgs& a, const ScMlpLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s);
+int sc_launch_nodes_policy_sampled(const ScArgs& a, const ScSampledLaunch<ScPolicyView>& p, int maxd_bucket, int W, int E, int K,
+                                   hipStream_t s);
+int sc_launch_nodes_mlp_sampled(const ScArgs& a, const ScSampledLaunch<ScMlpView>& p, int maxd_bucket, int W, int E, int K,
+                                hipStream_t s);
 
 // sc_reset_kernel's addressing without the reset: env n's observation at a.t of a.episode.
 __global__ __launch_bounds__(kScBlock) void sc_observe_kernel(const ScArgs a) {
@@ -54,6 +59,31 @@ __global__ __launch_bounds__(kPolicyActBlock) void sc_policy_act_kernel(const Sc
   }
   out0[n * A + q] = act;
   if (out1) out1[n * A + q] = act;
+}
+
+// The same with sampled actions (scg_sc_rollout_sampled): eps and, when given, samples are the
+// step's rows [N][A] of the call's noise and samples_out; a thread reads its element of the one
+// and then writes the same element of the other, so the two may be one buffer.
+__global__ __launch_bounds__(kPolicyActBlock) void sc_policy_act_sampled_kernel(const ScPolicyView pv, const void* obs,
+                                                                                 int obs_f64, int64_t N, int A, int O,
+                                                                                 float* out0, float* out1, const float* std,
+                                                                                 const float* eps, float* samples) {
+  const int64_t id = static_cast<int64_t>(blockIdx.x) * kPolicyActBlock + threadIdx.x;
+  if (id >= N * A) return;
+  const int q = static_cast<int>(id / N);
+  const int64_t n = id - static_cast<int64_t>(q) * N;
+  const float sd = std[q], e = eps[n * A + q];
+  float act, u;
+  if (obs_f64) {
+    const double* row = static_cast<const double*>(obs) + n * O;
+    act = sc_policy_action_sampled<kPolicyActChunk>(pv, O, n, q, [&](int j) { return static_cast<float>(row[j]); }, sd, e, &u);
+  } else {
+    const float* row = static_cast<const float*>(obs) + n * O;
+    act = sc_policy_action_sampled<kPolicyActChunk>(pv, O, n, q, [&](int j) { return row[j]; }, sd, e, &u);
+  }
+  out0[n * A + q] = act;
+  if (out1) out1[n * A + q] = act;
+  if (samples) samples[n * A + q] = u;
 }
 
 // sum = (add ? sum : 0.0) + r: the per-step path's reward_sum.
@@ -96,6 +126,34 @@ void sc_mlp_act_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t
   }
 }
 
+// The same with sampled actions: eps / samples as sc_policy_act_sampled_kernel's, the env's row
+// read and written by the env's thread.
+__global__ __launch_bounds__(kMlpActBlock) __attribute__((amdgpu_waves_per_eu(4)))
+void sc_mlp_act_sampled_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0,
+                               float* out1, const float* std, const float* eps, float* samples) {
+  extern __shared__ float hid_t[];  // [H][64]
+  const int64_t n = static_cast<int64_t>(blockIdx.x) * kMlpActBlock + threadIdx.x;
+  if (n >= N) return;
+  float* const hid = hid_t + threadIdx.x;
+  if (obs_f64) {
+    const double* row = static_cast<const double*>(obs) + n * O;
+    auto o = [&](int j) { return static_cast<float>(row[j]); };
+    for (int i = 0; i < mv.H; ++i) hid[i * kMlpActBlock] = sc_mlp_hidden<kMlpActChunk>(mv, O, n, i, o);
+  } else {
+    const float* row = static_cast<const float*>(obs) + n * O;
+    auto o = [&](int j) { return row[j]; };
+    for (int i = 0; i < mv.H; ++i) hid[i * kMlpActBlock] = sc_mlp_hidden<kMlpActChunk>(mv, O, n, i, o);
+  }
+  auto h = [&](int i) { return hid[i * kMlpActBlock]; };
+  for (int q = 0; q < A; ++q) {
+    float u;
+    const float act = sc_mlp_action_sampled<kMlpActChunk>(mv, O, n, q, h, std[q], eps[n * A + q], &u);
+    out0[n * A + q] = act;
+    if (out1) out1[n * A + q] = act;
+    if (samples) samples[n * A + q] = u;
+  }
+}
+
 // Whether hidden units fit the LDS the fused kernel has idle for them (a config scg_sc_prepare
 // has not derived an inbox for has none).
 bool sc_mlp_fits(const scg_sc_config* cfg, int32_t hidden) {
@@ -103,7 +161,8 @@ bool sc_mlp_fits(const scg_sc_config* cfg, int32_t hidden) {
 }
 
 // What the closed loop's host body needs of a policy: its argument check, whether it fuses
-// beyond the linear condition, and its two launches.
+// beyond the linear condition, and its launches: the action rows of one step (smp: the step's
+// rows of a sampled call's noise, or null) and the fused launch, deterministic or sampled.
 struct LinearHost {
   const scg_sc_policy* pol;
   int check() const {
@@ -115,13 +174,21 @@ struct LinearHost {
   bool fits(const scg_sc_config*) const { return true; }
   ScPolicyView view(int64_t N) const { return sc_policy_view(pol->params, pol->shared != 0, N, pol->act_lo, pol->act_hi); }
   static int act(const ScPolicyView& pv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1,
-                 hipStream_t s) {
+                 const ScSampleView* smp, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>((N * A + kPolicyActBlock - 1) / kPolicyActBlock));
+    if (smp) {
+      hipLaunchKernelGGL(sc_policy_act_sampled_kernel, grid, dim3(kPolicyActBlock), 0, s, pv, obs, obs_f64, N, A, O, out0, out1,
+                         smp->std, smp->noise, smp->samples);
+      return check_launch("sc_policy_act_sampled_kernel");
+    }
     hipLaunchKernelGGL(sc_policy_act_kernel, grid, dim3(kPolicyActBlock), 0, s, pv, obs, obs_f64, N, A, O, out0, out1);
     return check_launch("sc_policy_act_kernel");
   }
   static int fused(const ScArgs& a, const ScPolicyLaunch& p, int maxd, int W, int E, int K, hipStream_t s) {
     return sc_launch_nodes_policy(a, p, maxd, W, E, K, s);
+  }
+  static int fused(const ScArgs& a, const ScSampledLaunch<ScPolicyView>& p, int maxd, int W, int E, int K, hipStream_t s) {
+    return sc_launch_nodes_policy_sampled(a, p, maxd, W, E, K, s);
   }
 };
 
@@ -140,13 +207,22 @@ struct MlpHost {
     return sc_mlp_view(pol->params, pol->shared != 0, N, pol->hidden, pol->act_lo, pol->act_hi);
   }
   static int act(const ScMlpView& mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1,
-                 hipStream_t s) {
+                 const ScSampleView* smp, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>((N + kMlpActBlock - 1) / kMlpActBlock));
-    hipLaunchKernelGGL(sc_mlp_act_kernel, grid, dim3(kMlpActBlock), sizeof(float) * kMlpActBlock * mv.H, s, mv, obs, obs_f64, N, A, O, out0, out1);
+    const size_t lds = sizeof(float) * kMlpActBlock * mv.H;
+    if (smp) {
+      hipLaunchKernelGGL(sc_mlp_act_sampled_kernel, grid, dim3(kMlpActBlock), lds, s, mv, obs, obs_f64, N, A, O, out0, out1,
+                         smp->std, smp->noise, smp->samples);
+      return check_launch("sc_mlp_act_sampled_kernel");
+    }
+    hipLaunchKernelGGL(sc_mlp_act_kernel, grid, dim3(kMlpActBlock), lds, s, mv, obs, obs_f64, N, A, O, out0, out1);
     return check_launch("sc_mlp_act_kernel");
   }
   static int fused(const ScArgs& a, const ScMlpLaunch& p, int maxd, int W, int E, int K, hipStream_t s) {
     return sc_launch_nodes_mlp(a, p, maxd, W, E, K, s);
+  }
+  static int fused(const ScArgs& a, const ScSampledLaunch<ScMlpView>& p, int maxd, int W, int E, int K, hipStream_t s) {
+    return sc_launch_nodes_mlp_sampled(a, p, maxd, W, E, K, s);
   }
 };
 
@@ -155,12 +231,18 @@ bool sc_closed_fused(const scg_sc_config* cfg, const scg_sc_state* st) {
   return cfg->kernel == SCG_SC_KERNEL_NODES && !st->ledger;
 }
 
+// smp: the call's noise (scg_sc_rollout_sampled), or null: the deterministic loop.
 template <class Policy>
-int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const Policy& policy, void* obs_io,
-                      float* act_work, float* actions_out, void* obs_out, double* rewards_out, double* reward_sum,
-                      void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
+int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const Policy& policy,
+                      const scg_sc_sampling* smp, void* obs_io, float* act_work, float* actions_out, void* obs_out,
+                      double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags, int32_t* n_done,
+                      void* stream) {
   if (int rc = sc_host_check(cfg, st)) return rc;
   if (int rc = policy.check()) return rc;
+  if (smp) {
+    if (smp->reserved != 0) return fail(SCG_ERR_INVALID, "sampling: reserved must be 0");
+    if (n_steps > 0 && (!smp->std || !smp->noise)) return fail(SCG_ERR_INVALID, "sampling: device std and noise are required");
+  }
   if (!obs_io || !act_work || !reward_sum) return fail(SCG_ERR_INVALID, "obs_io/act_work/reward_sum buffers are required");
   if (n_steps < 0) return fail(SCG_ERR_INVALID, "rollout of %d steps", n_steps);
   if (flags & ~(SCG_BG_AUTORESET | SCG_SC_SERIAL)) return fail(SCG_ERR_INVALID, "unknown rollout flags");
@@ -183,6 +265,11 @@ int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_step
   const int A = cfg->n_actions, O = cfg->n_obs;
   const size_t obs_row = static_cast<size_t>(N) * O * (cfg->obs_f64 ? 8 : 4);
   auto pv = policy.view(N);
+  // rows k, k + 1, ... of the call's noise and samples
+  auto rows = [&](int32_t k) {
+    const int64_t at = sc_sample_index(N, A, k, 0, 0);
+    return ScSampleView{smp->std, smp->noise + at, smp->samples_out ? smp->samples_out + at : nullptr};
+  };
   int32_t crossed = 0;
   if (n_done) *n_done = 0;
   if (n_steps == 0) {
@@ -196,7 +283,8 @@ int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_step
     for (int32_t k = 0; k < n_steps; ++k) {
       const void* src = (k == 0 || !oo) ? obs_io : oo + obs_row * (k - 1);
       float* const arow = actions_out ? actions_out + static_cast<int64_t>(k) * N * A : nullptr;
-      if (int rc = Policy::act(pv, src, cfg->obs_f64, N, A, O, act_work, arow, s)) return rc;
+      const ScSampleView row = smp ? rows(k) : ScSampleView{};
+      if (int rc = Policy::act(pv, src, cfg->obs_f64, N, A, O, act_work, arow, smp ? &row : nullptr, s)) return rc;
       int32_t done = 0;
       double* const rrow = rewards_out + static_cast<int64_t>(k) * N;
       if (int rc = scg_sc_step(cfg, st, act_work, oo ? static_cast<void*>(oo + obs_row * k) : obs_io, rrow, terminal_obs,
@@ -223,10 +311,17 @@ int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_step
     a.rew = rewards_out ? rewards_out + static_cast<int64_t>(k0) * N : nullptr;
     a.t = st->time_step + 1;
     a.flags = (reset ? 2 : 0) | ((flags & SCG_SC_SERIAL) ? 4 : 0);
-    const ScClosedLaunch<decltype(pv)> p{pv, obs_io, act_work,
-                                         actions_out ? actions_out + static_cast<int64_t>(k0) * N * A : nullptr, reward_sum,
-                                         k0 > 0 ? 1 : 0};
-    if (int rc = Policy::fused(a, p, maxd, cfg->group, cfg->inbox_size, kc, s)) return rc;
+    float* const arows = actions_out ? actions_out + static_cast<int64_t>(k0) * N * A : nullptr;
+    const int32_t sum_add = k0 > 0 ? 1 : 0;
+    int rc;
+    if (smp) {
+      const ScSampledLaunch<decltype(pv)> p{pv, obs_io, act_work, arows, reward_sum, sum_add, rows(k0)};
+      rc = Policy::fused(a, p, maxd, cfg->group, cfg->inbox_size, kc, s);
+    } else {
+      const ScClosedLaunch<decltype(pv)> p{pv, obs_io, act_work, arows, reward_sum, sum_add};
+      rc = Policy::fused(a, p, maxd, cfg->group, cfg->inbox_size, kc, s);
+    }
+    if (rc) return rc;
     const int64_t end = static_cast<int64_t>(st->time_step) + kc;  // <= T without auto-reset
     if (reset) {
       crossed += static_cast<int32_t>(end / T);
@@ -262,14 +357,27 @@ int scg_sc_observe(const scg_sc_config* cfg, const scg_sc_state* st, void* obs, 
 int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_policy* policy,
                           void* obs_io, float* act_work, float* actions_out, void* obs_out, double* rewards_out,
                           double* reward_sum, void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
-  return sc_rollout_closed(cfg, st, n_steps, LinearHost{policy}, obs_io, act_work, actions_out, obs_out, rewards_out,
+  return sc_rollout_closed(cfg, st, n_steps, LinearHost{policy}, nullptr, obs_io, act_work, actions_out, obs_out, rewards_out,
                            reward_sum, terminal_obs, flags, n_done, stream);
 }
 
 int scg_sc_rollout_mlp(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_mlp* mlp, void* obs_io,
                        float* act_work, float* actions_out, void* obs_out, double* rewards_out, double* reward_sum,
                        void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
-  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, obs_io, act_work, actions_out, obs_out, rewards_out, reward_sum,
+  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, nullptr, obs_io, act_work, actions_out, obs_out, rewards_out, reward_sum,
+                           terminal_obs, flags, n_done, stream);
+}
+
+int scg_sc_rollout_sampled(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_policy* linear,
+                           const scg_sc_mlp* mlp, const scg_sc_sampling* smp, void* obs_io, float* act_work, float* actions_out,
+                           void* obs_out, double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags,
+                           int32_t* n_done, void* stream) {
+  if (!linear == !mlp) return fail(SCG_ERR_INVALID, "sampled rollout: exactly one of the linear policy and the mlp");
+  if (!smp) return fail(SCG_ERR_INVALID, "sampled rollout: the sampling struct is required");
+  if (linear)
+    return sc_rollout_closed(cfg, st, n_steps, LinearHost{linear}, smp, obs_io, act_work, actions_out, obs_out, rewards_out,
+                             reward_sum, terminal_obs, flags, n_done, stream);
+  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, smp, obs_io, act_work, actions_out, obs_out, rewards_out, reward_sum,
                            terminal_obs, flags, n_done, stream);
 }
 

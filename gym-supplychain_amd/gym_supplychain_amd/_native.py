@@ -141,6 +141,12 @@ class ScMlp(ctypes.Structure):
                 ("params", ctypes.c_void_p)]
 
 
+class ScSampling(ctypes.Structure):
+    """scg_sc_sampling (include/scgpu.h): the std, noise and samples of scg_sc_rollout_sampled."""
+    _fields_ = [("std", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("samples_out", ctypes.c_void_p),
+                ("reserved", ctypes.c_int64)]
+
+
 class BgServerLine(ctypes.Structure):
     """scg_bg_server_line (include/scgpu.h): one slot's 64-byte request line."""
     _fields_ = [("req_seq", ctypes.c_uint32), ("cmd", ctypes.c_int32), ("wpack", ctypes.c_uint32),
@@ -314,6 +320,11 @@ SIGNATURES = {
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_uint32, _i32p, ctypes.c_void_p]),
     "scg_sc_mlp_fused": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_int32]),
+    "scg_sc_rollout_sampled": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_int32,
+                                              ctypes.POINTER(ScPolicy), ctypes.POINTER(ScMlp), ctypes.POINTER(ScSampling),
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _i32p,
+                                              ctypes.c_void_p]),
     "scg_sc_draw_tables": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_uint32,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_nodes_max_blocks": (ctypes.c_int, [ctypes.c_int32]),

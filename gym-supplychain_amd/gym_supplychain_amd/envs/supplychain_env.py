@@ -239,12 +239,13 @@ def pack_mlp_words(w1, b1, w2, b2):
 class ScPolicyRollout:
     """What SupplyChainVecEnv.rollout_policy returns: `reward_sum` float64 [N], `last_obs`
     [N, n_obs] (the env's own buffer: clone() to keep it), `dones` CPU bool [K], and `actions`
-    float32 [K, N, A], `obs` [K, N, n_obs], `rewards` float64 [K, N] where requested, else None."""
-    __slots__ = ("reward_sum", "last_obs", "dones", "actions", "obs", "rewards")
+    float32 [K, N, A], `obs` [K, N, n_obs], `rewards` float64 [K, N] where requested, else None;
+    `samples` the samples_out tensor of a sampled call (the actions before their clamp), else None."""
+    __slots__ = ("reward_sum", "last_obs", "dones", "actions", "obs", "rewards", "samples")
 
-    def __init__(self, reward_sum, last_obs, dones, actions=None, obs=None, rewards=None):
+    def __init__(self, reward_sum, last_obs, dones, actions=None, obs=None, rewards=None, samples=None):
         self.reward_sum, self.last_obs, self.dones = reward_sum, last_obs, dones
-        self.actions, self.obs, self.rewards = actions, obs, rewards
+        self.actions, self.obs, self.rewards, self.samples = actions, obs, rewards, samples
 
 
 class SupplyChainVecEnv:
@@ -255,6 +256,7 @@ class SupplyChainVecEnv:
     rollout(actions float32 [K, N, n_actions]) -> (obs [K, N, n_obs], rewards [K, N], dones [K]): K steps, one call
     rollout_policy(weights, bias, n_steps) -> ScPolicyRollout: K steps with a linear policy's actions computed on the device
     rollout_policy(pack_mlp(w1, b1, w2, b2), None, n_steps): the same with a one-hidden-layer ReLU policy
+    rollout_policy(..., noise=eps, std=s, samples_out=u): either policy with sampled actions, clip(z + s * eps[k])
     observe() -> obs [N, n_obs]: the current observation, whatever call left the state
 
     Returned tensors are this env's output buffers (clone() to keep them). With
@@ -618,8 +620,32 @@ class SupplyChainVecEnv:
             nat.check(-rc)
         return bool(rc)
 
+    def _sampling(self, K, noise, std, samples_out):
+        """The checked (noise, std on the device, samples_out) of a sampled rollout_policy call."""
+        N, A = self.n_envs, self.n_actions
+        if noise is None or std is None:
+            raise ValueError("noise and std go together" if noise is not None or std is not None else
+                             "samples_out needs noise and std")
+        for name, x in (("noise", noise), ("samples_out", samples_out)):
+            if x is None:
+                continue
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != self.device or \
+                    tuple(x.shape) != (K, N, A) or not x.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 tensor [{K}, {N}, {A}] on {self.device}")
+        try:
+            sd = torch.as_tensor(std, dtype=torch.float32).detach().to(self.device)
+        except (TypeError, RuntimeError) as e:
+            raise ValueError(f"std must be a float or float32 [{A}]: {e}") from None
+        if sd.dim() == 0:
+            sd = sd.expand(A)
+        if tuple(sd.shape) != (A,):
+            raise ValueError(f"std must be a float or have shape [{A}], got {list(sd.shape)}")
+        if not bool((torch.isfinite(sd) & (sd >= 0)).all()):  # the call's one host read
+            raise ValueError("std must be finite and >= 0")
+        return noise, sd.contiguous(), samples_out
+
     def rollout_policy(self, weights, bias=None, n_steps=None, clip=None, return_actions=False, return_obs=False,
-                       return_rewards=False):
+                       return_rewards=False, noise=None, std=None, samples_out=None):
         """n_steps steps with every env's action row computed on the device from the
         observation o the env last produced (scg_sc_rollout_policy), all in float32, each
         multiply and add rounded on its own, in this order:
@@ -645,7 +671,23 @@ class SupplyChainVecEnv:
             h[i] = b1[i];  for j in range(n_obs): h[i] = h[i] + w1[i][j] * o[j];  h[i] = h[i] if h[i] > 0 else +0.0
             z[a] = b2[a];  for i in range(H): z[a] = z[a] + w2[a][i] * h[i]
 
-        clipped as above; mlp_fused(H) tells whether the steps run in one launch."""
+        clipped as above; mlp_fused(H) tells whether the steps run in one launch.
+
+        Sampled actions, for policy-gradient training (scg_sc_rollout_sampled): with noise, a
+        contiguous float32 tensor [n_steps, N, A] on the env's device, and std, a float or
+        anything convertible to float32 [A] (finite, >= 0; one std per action for every env), the
+        action of either policy is the clip of
+
+            u[a] = z[a] + (std[a] * noise[k][n][a])     the product rounded to float32, then the sum
+
+        with z as above and k the step's index in this call, 0 .. n_steps-1: the rows count on
+        across auto-resets inside the call, and a caller who cuts an episode into several calls
+        gives each call its own rows (the state persists between calls). Both or neither of noise
+        and std. The noise is only read; it is the caller's to draw (torch.randn, antithetic
+        pairs, OU noise). samples_out, None or a tensor like noise, receives u, what the
+        log-probability is taken of; it may be noise itself, which is then overwritten. The
+        result's `samples` is that tensor. A full episode of 360 steps of 65,536 envs with 14
+        actions is 1.3 GB of noise. Without noise the call is the deterministic one above."""
         N, A, O = self.n_envs, self.n_actions, self.n_obs
         if isinstance(weights, (ScPackedPolicy, ScPackedMlp)):
             if bias is not None:
@@ -667,13 +709,16 @@ class SupplyChainVecEnv:
         if getattr(self, "_pol_obs", None) is None:  # the call's own buffers, kept for the next
             self._pol_obs = torch.empty((N, O), dtype=self.obs_dtype, device=dev)
             self._pol_act = torch.empty((N, A), dtype=torch.float32, device=dev)
+        sampled = noise is not None or std is not None or samples_out is not None
+        if sampled:
+            noise, std, samples_out = self._sampling(K, noise, std, samples_out)
         mlp = isinstance(packed, ScPackedMlp)
         fused = self.mlp_fused(packed.hidden) if mlp else self.kernel == "nodes" and not self.build_info
         rewards = torch.empty((K, N), dtype=torch.float64, device=dev) if (return_rewards or not fused) else None
         res = ScPolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), self._pol_obs, None,
                               torch.empty((K, N, A), dtype=torch.float32, device=dev) if return_actions else None,
                               torch.empty((K, N, O), dtype=self.obs_dtype, device=dev) if return_obs else None,
-                              rewards if return_rewards else None)
+                              rewards if return_rewards else None, samples_out)
         t0, T = self._st.time_step, self.spec.total_time_steps
         if t0 >= 0:  # (before a reset the library refuses below)
             self.observe(self._pol_obs)
@@ -686,7 +731,15 @@ class SupplyChainVecEnv:
                                packed.params.data_ptr())
             entry = nat.lib.scg_sc_rollout_policy
         n_done = ctypes.c_int32(0)
-        nat.check(entry(self._cfg_ref, self._st_ref, int(n_steps), ctypes.byref(pol),
+        if sampled:
+            smp = nat.ScSampling(std.data_ptr(), noise.data_ptr(),
+                                 samples_out.data_ptr() if samples_out is not None else None, 0)
+            pols = (None, ctypes.byref(pol)) if mlp else (ctypes.byref(pol), None)
+            head = (*pols, ctypes.byref(smp))
+            entry = nat.lib.scg_sc_rollout_sampled
+        else:
+            head = (ctypes.byref(pol),)
+        nat.check(entry(self._cfg_ref, self._st_ref, int(n_steps), *head,
                         self._pol_obs.data_ptr(), self._pol_act.data_ptr(), nat.ptr(res.actions), nat.ptr(res.obs),
                         nat.ptr(rewards), res.reward_sum.data_ptr(), self._term_ptr, self._flags, ctypes.byref(n_done),
                         self._stream()))

@@ -50,7 +50,9 @@ extern "C" {
  *   scg_sc_observe and scg_sc_rollout_policy (scg_sc_policy: the closed-loop SupplyChain
  *   rollout with a linear policy, per env or shared), added entry points; also
  *   scg_sc_rollout_mlp and scg_sc_mlp_fused (scg_sc_mlp: the same closed loop with a
- *   one-hidden-layer ReLU policy), added entry points. */
+ *   one-hidden-layer ReLU policy), added entry points; also scg_sc_rollout_sampled
+ *   (scg_sc_sampling: either closed loop with the caller's noise added to the action before
+ *   its clamp, for policy-gradient training), an added entry point. */
 #define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
@@ -738,6 +740,45 @@ SCG_API int scg_sc_rollout_mlp(const scg_sc_config* cfg, scg_sc_state* st, int32
                                double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags,
                                int32_t* n_done, void* stream);
 SCG_API int scg_sc_mlp_fused(const scg_sc_config* cfg, const scg_sc_state* st, int32_t hidden);
+
+/*
+ * Either closed loop with sampled actions. With z_a the linear policy's or the MLP's output
+ * before its clamp, exactly as above, one standard deviation per action and noise the caller
+ * supplies (the library draws none):
+ *   u_a   = z_a + (std_a * eps[k][n][a])      the product rounded to float32, then the sum; no FMA
+ *   act_a = !(u_a >= act_lo) ? act_lo : (u_a > act_hi ? act_hi : u_a)
+ * k is the step's index within this call, 0 .. n_steps-1: it counts on across the launches the
+ * call is cut into and across auto-resets inside it (a caller who cuts an episode into several
+ * calls passes each call its own rows). A NaN u (a NaN z; 0 * inf) gives act_lo. Exactly one of
+ * linear / mlp is non-NULL. Everything else is the contract of scg_sc_rollout_policy /
+ * scg_sc_rollout_mlp unchanged: actions_out and act_work hold the clamped actions, everything
+ * but the actions is what scg_sc_rollout gives for them bit for bit, the buffers, flags and
+ * error codes keep their meaning, the fused and the per-step path are chosen as there
+ * (scg_sc_mlp_fused answers for the sampled MLP too).
+ *   std          DEVICE float32 [n_actions], for every env. The library cannot read it on the
+ *                host and takes the values as they are: a negative, infinite or NaN std goes
+ *                into the formula like any other float.
+ *   noise        DEVICE float32 [K][N][n_actions], K = n_steps: only read
+ *   samples_out  DEVICE float32 [K][N][n_actions] or NULL: u, the sample before the clamp (what
+ *                the log-probability is taken of). It may be the noise buffer itself: every
+ *                element is read and then written by one thread. Any other overlap of the two
+ *                is the caller's error.
+ * Checked before any HIP call, st left untouched: SCG_ERR_INVALID when both or neither of
+ * linear / mlp is given, for a NULL smp, for a NULL std or noise with n_steps > 0, for
+ * reserved != 0, and for everything the two deterministic entry points refuse.
+ */
+typedef struct scg_sc_sampling {
+  const float* std;    /* DEVICE float32 [n_actions]: one std per action, for every env */
+  const float* noise;  /* DEVICE float32 [K][N][n_actions] */
+  float* samples_out;  /* DEVICE float32 [K][N][n_actions] or NULL: u before the clamp; may equal noise */
+  int64_t reserved;    /* 0 */
+} scg_sc_sampling;     /* 32 bytes */
+
+SCG_API int scg_sc_rollout_sampled(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps,
+                                   const scg_sc_policy* linear, const scg_sc_mlp* mlp, const scg_sc_sampling* smp,
+                                   void* obs_io, float* act_work, float* actions_out, void* obs_out,
+                                   double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags,
+                                   int32_t* n_done, void* stream);
 
 /* The per-episode tables scg_sc_step draws (for tests): demand DEVICE int32
  * [N][T+1][R][P], leadtimes DEVICE int32 [N][T][n_leadtimes] (NULL when deterministic). */
