@@ -37,6 +37,7 @@ SCG_SC_POLICY_HD int sc_mlp_word(int O, int H, int layer, int r, int k) {
 constexpr int sc_mlp_fused_hidden_max(int inbox_size, int n_nodes) { return 2 * (inbox_size + n_nodes); }
 
 struct ScMlpView {
+  static constexpr bool kMlp = true;
   const float* params;
   int64_t qstride, nstride;
   float lo, hi;
@@ -65,23 +66,27 @@ SCG_SC_POLICY_HD float sc_mlp_hidden(const ScMlpView& mv, int O, int64_t n, int 
   return sc_mlp_relu(sc_policy_row_sum<kChunk>(row, mv.qstride, O, obs));
 }
 
-// Action a of env n from its hidden units hid(i), i = 0 .. H-1.
+// The value z_a of env n before its clamp (scg_sc_policy.h: sc_policy_clamp, sc_policy_clamp_sampled),
+// from the env's hidden units hid(i), i = 0 .. H-1.
 template <int kChunk, class Hid>
-SCG_SC_POLICY_HD float sc_mlp_action(const ScMlpView& mv, int O, int64_t n, int a, const Hid& hid) {
+SCG_SC_POLICY_HD float sc_mlp_z(const ScMlpView& mv, int O, int64_t n, int a, const Hid& hid) {
   const float* row = mv.params + sc_mlp_param_index(mv, O, n, 1, a, 0);
-  return sc_policy_clamp(sc_policy_row_sum<kChunk>(row, mv.qstride, mv.H, hid), mv.lo, mv.hi);
+  return sc_policy_row_sum<kChunk>(row, mv.qstride, mv.H, hid);
 }
 
-// The same action sampled (scg_sc_policy.h sc_policy_sample): u (stored to *u_out) and its clamp.
+// Action a of env n in one call, deterministic and sampled (scg_sc_policy.h sc_policy_action):
+// sc_mlp_z under the two finishes.
+template <int kChunk, class Hid>
+SCG_SC_POLICY_HD float sc_mlp_action(const ScMlpView& mv, int O, int64_t n, int a, const Hid& hid) {
+  return sc_policy_clamp(sc_mlp_z<kChunk>(mv, O, n, a, hid), mv.lo, mv.hi);
+}
 template <int kChunk, class Hid>
 SCG_SC_POLICY_HD float sc_mlp_action_sampled(const ScMlpView& mv, int O, int64_t n, int a, const Hid& hid, float std, float eps,
                                              float* u_out) {
-  const float* row = mv.params + sc_mlp_param_index(mv, O, n, 1, a, 0);
-  const float u = sc_policy_sample(sc_policy_row_sum<kChunk>(row, mv.qstride, mv.H, hid), std, eps);
-  *u_out = u;
-  return sc_policy_clamp(u, mv.lo, mv.hi);
+  return sc_policy_clamp_sampled(sc_mlp_z<kChunk>(mv, O, n, a, hid), std, eps, mv.lo, mv.hi, u_out);
 }
 
-using ScMlpLaunch = ScClosedLaunch<ScMlpView>;
+static_assert(sizeof(ScSampledLaunch<ScMlpView>) == sizeof(ScClosedLaunch<ScMlpView>) + sizeof(ScSampleView),
+              "the kernel arguments: smp directly behind the common fields");
 
 }  // namespace scg

@@ -28,11 +28,12 @@
 // node after node in the reference's order (sc_nodes_serial). Observations and actions go
 // through LDS tiles so HBM sees whole rows; the state pointers stay the batch's base
 // pointers (ScEnv soff/hoff) so they live in SGPRs.
-// The same tile code runs under four more drivers: the rollout kernel (a step loop inside the
-// tile loop, the state in LDS between a launch's steps), the two closed-loop rollout kernels
-// (the same, with each step's action tile computed from the previous step's observation tile
-// by a linear policy, scg_sc_policy.h, or a one-hidden-layer ReLU policy, scg_sc_mlp.h) and the
-// step server (one resident block serving a drop-in env's steps).
+// The same tile code runs under three more drivers: the rollout kernel (a step loop inside the
+// tile loop, the state in LDS between a launch's steps), the closed-loop rollout kernel (the
+// same, with each step's action tile computed from the previous step's observation tile by a
+// linear policy, scg_sc_policy.h, or a one-hidden-layer ReLU policy, scg_sc_mlp.h, deterministic
+// or with the caller's noise added: four instantiations per (MAXD, F64)) and the step server
+// (one resident block serving a drop-in env's steps).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -74,8 +75,7 @@ struct ScAcc {  // a marker: a non-null ScEnv::dbg turns the section stamps on
 #include "scg_supplychain_core.h"
 #include "scg_supplychain_args.h"
 #include "scg_supplychain_nodes.h"
-#include "scg_sc_policy.h"
-#include "scg_sc_mlp.h"
+#include "scg_sc_nodes_launch.h"
 
 // Diagnostic build only (-DSCG_NODES_STAMPS, tools/nodes_stamps.py): lane 0 of every wave
 // records the shader clock at the phase boundaries (0 start, 5 heaps staged, 6 past the first
@@ -201,10 +201,10 @@ struct NodesRolloutStep {
   __device__ __forceinline__ bool write_back() const { return write_back_; }
 };
 
-// Step k of a closed-loop launch (sc_policy_rollout_nodes_kernel, sc_mlp_rollout_nodes_kernel):
-// a rollout step whose action tile is not loaded but computed, from the observation tile the
-// previous step left (kPolicy: the parts of sc_nodes_tile that differ), by the policy Launch
-// carries (ScPolicyLaunch: linear; ScMlpLaunch: one hidden layer). Every output is optional;
+// Step k of a closed-loop launch (sc_closed_rollout_nodes_kernel): a rollout step whose action
+// tile is not loaded but computed, from the observation tile the previous step left (kPolicy:
+// the parts of sc_nodes_tile that differ), by the policy Launch carries (its pv an ScPolicyView:
+// linear; an ScMlpView, kMlp: one hidden layer). Every output is optional;
 // first() / last(): the tile's first and last step in the launch, where obs_io is read and
 // obs_io, act_work and reward_sum are written. A sampled launch (ScSampledLaunch, kSampled)
 // adds the caller's noise to every action before its clamp: noise(x, n, row) is env n's part of
@@ -220,7 +220,7 @@ struct NodesClosedStep {
   static constexpr bool kStreamOut = true;
   static constexpr bool kObsOptional = true;
   static constexpr bool kPolicy = true;
-  static constexpr bool kMlp = std::is_same<decltype(Launch::pv), ScMlpView>::value;
+  static constexpr bool kMlp = Launch::kMlp;
   static constexpr bool kSampled = Launch::kSampled;
   const Launch& p;
   int32_t t_, flags_;
@@ -251,41 +251,12 @@ struct NodesClosedStep {
     return NodesNoise{p.smp.std, p.smp.noise + at, p.smp.samples ? p.smp.samples + at : nullptr};
   }
 };
-using NodesPolicyStep = NodesClosedStep<ScPolicyLaunch>;
-using NodesMlpStep = NodesClosedStep<ScMlpLaunch>;
 
 // The closed loop's product: wave w computes actions w, w + W, ... of its lane's env (n) from
 // the env's row of the observation tile into its row of the action tile. The observation
 // elements are LDS reads at an odd row stride (lanes on distinct banks); an action's parameter
 // words (O weights and the bias) are requested together, up to kNodesPolicyChunk per round.
 constexpr int kNodesPolicyChunk = 32;
-template <class ObsT>
-__device__ __forceinline__ void sc_nodes_policy_act(const ScPolicyView& pv, int A, int O, int64_t n, int w, int W,
-                                                    const ObsT* orow, float* arow) {
-  auto o = [&](int j) { return static_cast<float>(orow[j]); };
-  for (int q = w; q < A; q += W) arow[q] = sc_policy_action<kNodesPolicyChunk>(pv, O, n, q, o);
-}
-
-// The closed loop's MLP (kMlp steps): wave w computes hidden units w, w + W, ... of its lane's
-// env from the env's row of the observation tile into the hidden tile [H][64] (float, unit-major,
-// lane fastest: the lanes of a wave on consecutive banks; `hid` is the lane's column); past a
-// barrier it computes actions w, w + W, ... from that column into the env's row of the action
-// tile. Every thread of the block calls it (live: the lane has an env). The hidden tile lies
-// over the inbox values and the cost rows, idle where this runs (the note at the end of
-// sc_nodes_tile); the launcher admits only H <= 2 * (E + NN).
-template <class ObsT>
-__device__ __forceinline__ void sc_nodes_mlp_act(const ScMlpView& mv, int A, int O, int64_t n, bool live, int w, int W,
-                                                 const ObsT* orow, float* arow, float* hid) {
-  if (live) {
-    auto o = [&](int j) { return static_cast<float>(orow[j]); };
-    for (int i = w; i < mv.H; i += W) hid[i * 64] = sc_mlp_hidden<kNodesPolicyChunk>(mv, O, n, i, o);
-  }
-  __syncthreads();
-  if (live) {
-    auto h = [&](int i) { return hid[i * 64]; };
-    for (int q = w; q < A; q += W) arow[q] = sc_mlp_action<kNodesPolicyChunk>(mv, O, n, q, h);
-  }
-}
 
 // The sampled closed loop (kSampled steps): the same products with the caller's noise added
 // before the clamp (scg_sc_policy.h sc_policy_sample). The thread that computes action q of its
@@ -303,48 +274,95 @@ __device__ __forceinline__ void sc_nodes_noise_request(const NodesNoise& nz, int
 #pragma unroll
   for (int u = 0; u < kNodesNoiseAhead; ++u) ev[u] = w + u * W < A ? nz.eps[w + u * W] : 0.0f;
 }
-// Actions w, w + W, ... of the lane's env: act(q, std, eps, &u) is the policy's sampled action q.
-template <class Act>
-__device__ __forceinline__ void sc_nodes_sampled_actions(const NodesNoise& nz, int A, int w, int W,
-                                                         const float (&ev)[kNodesNoiseAhead], float* arow, const Act& act) {
-  auto one = [&](int q, float eps) {
-    float u;
-    arow[q] = act(q, nz.std[q], eps, &u);
-    if (nz.out) __hip_atomic_store(&nz.out[q], u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+
+// Actions w, w + W, ... of the lane's env into its row of the action tile, each the finish
+// (scg_sc_policy.h) of z(q), the policy's value of action q before its clamp: the clamp to
+// pv.lo .. pv.hi, or for a sampled step the clamp of the sample, with the noise nz and its
+// elements requested ahead, ev (neither is read when !kSampled).
+template <bool kSampled, class View, class Z>
+__device__ __forceinline__ void sc_nodes_actions(const View& pv, int A, int w, int W, float* arow, const Z& z,
+                                                 const NodesNoise& nz, const float (&ev)[kNodesNoiseAhead]) {
+  if constexpr (kSampled) {
+    auto one = [&](int q, float eps) {
+      const float sd = nz.std[q];
+      float u;
+      arow[q] = sc_policy_clamp_sampled(z(q), sd, eps, pv.lo, pv.hi, &u);
+      if (nz.out) __hip_atomic_store(&nz.out[q], u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
 #pragma unroll
-  for (int u = 0; u < kNodesNoiseAhead; ++u)
-    if (w + u * W < A) one(w + u * W, ev[u]);
-  for (int q = w + kNodesNoiseAhead * W; q < A; q += W) one(q, nz.eps[q]);
+    for (int u = 0; u < kNodesNoiseAhead; ++u)
+      if (w + u * W < A) one(w + u * W, ev[u]);
+    for (int q = w + kNodesNoiseAhead * W; q < A; q += W) one(q, nz.eps[q]);
+  } else {
+    for (int q = w; q < A; q += W) arow[q] = sc_policy_clamp(z(q), pv.lo, pv.hi);
+  }
 }
 
-template <class ObsT>
-__device__ __forceinline__ void sc_nodes_policy_act_sampled(const ScPolicyView& pv, int A, int O, int64_t n, int w, int W,
-                                                            const ObsT* orow, float* arow, const NodesNoise& nz) {
-  float ev[kNodesNoiseAhead];
-  sc_nodes_noise_request(nz, A, w, W, ev);
-  auto o = [&](int j) { return static_cast<float>(orow[j]); };
-  sc_nodes_sampled_actions(nz, A, w, W, ev, arow, [&](int q, float sd, float eps, float* u) {
-    return sc_policy_action_sampled<kNodesPolicyChunk>(pv, O, n, q, o, sd, eps, u);
-  });
-}
-
-// (sc_nodes_mlp_act's two stages and barrier; every thread of the block calls it.)
-template <class ObsT>
-__device__ __forceinline__ void sc_nodes_mlp_act_sampled(const ScMlpView& mv, int A, int O, int64_t n, bool live, int w, int W,
-                                                         const ObsT* orow, float* arow, float* hid, const NodesNoise& nz) {
-  float ev[kNodesNoiseAhead];
-  if (live) {
+// The linear policy's act, for step sp.k_ + ahead of the launch (its noise row).
+template <class Step, class ObsT>
+__device__ __forceinline__ void sc_nodes_policy_act(const Step& sp, const ScArgs& a, int ahead, int64_t n, int w, int W,
+                                                    const ObsT* orow, float* arow) {
+  const ScPolicyView& pv = sp.p.pv;
+  const int A = a.c.A, O = a.c.O;
+  // the sampled step's alone: a deterministic step sets neither, and sc_nodes_actions<false>
+  // reads neither
+  [[maybe_unused]] NodesNoise nz{};
+  [[maybe_unused]] float ev[kNodesNoiseAhead];
+  if constexpr (Step::kSampled) {
+    nz = sp.noise(a, n, sp.k_ + ahead);
     sc_nodes_noise_request(nz, A, w, W, ev);
+  }
+  auto o = [&](int j) { return static_cast<float>(orow[j]); };
+  sc_nodes_actions<Step::kSampled>(pv, A, w, W, arow,
+                                   [&](int q) { return sc_policy_z<kNodesPolicyChunk>(pv, O, n, q, o); }, nz, ev);
+}
+
+// The MLP's act (kMlp steps): wave w computes hidden units w, w + W, ... of its lane's env from
+// the env's row of the observation tile into the hidden tile [H][64] (float, unit-major, lane
+// fastest: the lanes of a wave on consecutive banks; `hid` is the lane's column); past a
+// barrier it computes actions w, w + W, ... from that column into the env's row of the action
+// tile. Every thread of the block calls it (live: the lane has an env). The hidden tile lies
+// over the inbox values and the cost rows, idle where this runs (the note at the end of
+// sc_nodes_tile); the launcher admits only H <= 2 * (E + NN).
+template <class Step, class ObsT>
+__device__ __forceinline__ void sc_nodes_mlp_act(const Step& sp, const ScArgs& a, int ahead, int64_t n, bool live, int w, int W,
+                                                 const ObsT* orow, float* arow, float* hid) {
+  const ScMlpView& mv = sp.p.pv;
+  const int A = a.c.A, O = a.c.O;
+  // the sampled step's alone: a deterministic step sets neither, and sc_nodes_actions<false>
+  // reads neither
+  [[maybe_unused]] NodesNoise nz{};
+  [[maybe_unused]] float ev[kNodesNoiseAhead];
+  if constexpr (Step::kSampled) nz = sp.noise(a, n, sp.k_ + ahead);
+  if (live) {
+    if constexpr (Step::kSampled) sc_nodes_noise_request(nz, A, w, W, ev);
     auto o = [&](int j) { return static_cast<float>(orow[j]); };
     for (int i = w; i < mv.H; i += W) hid[i * 64] = sc_mlp_hidden<kNodesPolicyChunk>(mv, O, n, i, o);
   }
   __syncthreads();
   if (live) {
     auto h = [&](int i) { return hid[i * 64]; };
-    sc_nodes_sampled_actions(nz, A, w, W, ev, arow, [&](int q, float sd, float eps, float* u) {
-      return sc_mlp_action_sampled<kNodesPolicyChunk>(mv, O, n, q, h, sd, eps, u);
-    });
+    sc_nodes_actions<Step::kSampled>(mv, A, w, W, arow,
+                                     [&](int q) { return sc_mlp_z<kNodesPolicyChunk>(mv, O, n, q, h); }, nz, ev);
+  }
+}
+
+// A closed-loop step's act, whichever of the four its launch is: the actions of every live env
+// of the tile for step sp.k_ + ahead of the launch (ahead 0: this step's own, at the launch's
+// first step; 1: the next step's), from the observation tile (orow: the lane's row) into the
+// action tile act_t; `idle` is the LDS the MLP's hidden tile lies over. Every thread of the block
+// calls it (the MLP's barrier). Two things are left to the callees because done by the caller they
+// moved pinned instruction counts: the lane's action row is addressed here, for
+// the linear policy under `live`, and the noise row is counted from sp.k_ where the noise is
+// looked up.
+template <class Step, class ObsT>
+__device__ __forceinline__ void sc_nodes_closed_act(const Step& sp, const ScArgs& a, int ahead, int64_t n, int lane, bool live,
+                                                    int w, int W, const ObsT* orow, float* act_t, double* idle) {
+  const int Ap = a.c.A | 1;
+  if constexpr (Step::kMlp) {
+    sc_nodes_mlp_act(sp, a, ahead, n, live, w, W, orow, act_t + lane * Ap, reinterpret_cast<float*>(idle) + lane);
+  } else if (live) {
+    sc_nodes_policy_act(sp, a, ahead, n, w, W, orow, act_t + lane * Ap);
   }
 }
 
@@ -414,19 +432,8 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw.next()) obs_t[tw.r * Op + tw.k] = src[q];
       if (w == 0 && live) rsum[lane] = sp.p.sum_add ? sp.p.reward_sum[n] : 0.0;
       __syncthreads();
-      if constexpr (Step::kSampled) {  // the noise row of this step: the launch's first
-        if constexpr (Step::kMlp) {
-          sc_nodes_mlp_act_sampled(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap,
-                                   reinterpret_cast<float*>(ibval) + lane, sp.noise(a, n, 0));
-        } else if (live) {
-          sc_nodes_policy_act_sampled(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap, sp.noise(a, n, 0));
-        }
-      } else if constexpr (Step::kMlp) {
-        sc_nodes_mlp_act(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap,
-                         reinterpret_cast<float*>(ibval) + lane);
-      } else if (live) {
-        sc_nodes_policy_act(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap);
-      }
+      // (the noise row of this step: the launch's first)
+      sc_nodes_closed_act(sp, a, 0, n, lane, live, w, W, orow, act_t, ibval);
     }
   }
 
@@ -656,17 +663,8 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
       for (int q = threadIdx.x; q < nb * c.O; q += blockDim.x, tw2.next())
         __hip_atomic_store(&dst[q], obs_t[tw2.r * Op + tw2.k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (w == 0 && live) sp.p.reward_sum[n] = rsum[lane];
-    } else if constexpr (Step::kSampled) {  // the next step's noise row (this is not the launch's last step)
-      if constexpr (Step::kMlp) {
-        sc_nodes_mlp_act_sampled(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap,
-                                 reinterpret_cast<float*>(ibval) + lane, sp.noise(a, n, sp.k_ + 1));
-      } else if (live) {
-        sc_nodes_policy_act_sampled(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap, sp.noise(a, n, sp.k_ + 1));
-      }
-    } else if constexpr (Step::kMlp) {
-      sc_nodes_mlp_act(sp.p.pv, c.A, c.O, n, live, w, W, orow, act_t + lane * Ap, reinterpret_cast<float*>(ibval) + lane);
-    } else if (live) {
-      sc_nodes_policy_act(sp.p.pv, c.A, c.O, n, w, W, orow, act_t + lane * Ap);
+    } else {  // the next step's noise row (this is not the launch's last step)
+      sc_nodes_closed_act(sp, a, 1, n, lane, live, w, W, orow, act_t, ibval);
     }
   }
   if (live) {  // the stocks of this wave's nodes back, one 64-env row per instruction (the
@@ -697,9 +695,11 @@ __device__ __forceinline__ void sc_nodes_tile(const ScArgs& a, int64_t tile, int
   // barrier, past which the next step's act phase first writes it. A tile's first step in a
   // launch opens with a barrier of its own before it overwrites the observation tile the
   // block's previous tile may still be copying out.
-  // The MLP closed loop keeps its hidden tile [H][64] (float) over ibval and cost_v, which are
-  // adjacent: (E + NN) * 512 bytes, H <= 2 * (E + NN) units (sc_mlp_fused_hidden_max; the
-  // launcher refuses more). It is written and read only inside sc_nodes_mlp_act, i.e. at
+  // All four instantiations of the closed-loop kernel (linear or MLP, deterministic or sampled)
+  // share that picture; the noise of a sampled step touches no LDS. The two MLP instantiations
+  // keep their hidden tile [H][64] (float) over ibval and cost_v, which are adjacent:
+  // (E + NN) * 512 bytes, H <= 2 * (E + NN) units (sc_mlp_fused_hidden_max; the launcher
+  // refuses more). It is written and read only inside sc_nodes_mlp_act, i.e. at
   // first() past the obs_io load's barrier and after a step's last barrier (the auto-reset
   // one included). That is safe because
   //  - the region's last read in a step lies before that step's last barrier: ibval by the
@@ -809,123 +809,38 @@ void sc_rollout_nodes_kernel(const ScArgs a_arg, int W, int E, int K, int obs_mo
 }
 
 // ---- closed-loop rollout: the rollout kernel with the action tile computed on chip --------
-// (scg_sc_rollout_policy, csrc/scg_sc_policy.h.) The rollout kernel's block, LDS layout,
-// persistent tile loop and step loop under NodesPolicyStep: a tile's first step in the launch
-// loads its envs' last observation rows (obs_io) into the observation tile and computes the
-// first action tile from it; after every other step each wave computes its share of the next
-// action tile from the observation tile the step just completed, so between two kept steps
-// nothing crosses HBM but the policy's parameter words (and the outputs asked for). The
+// (scg_sc_rollout_policy, scg_sc_rollout_mlp, scg_sc_rollout_sampled; csrc/scg_sc_policy.h,
+// csrc/scg_sc_mlp.h.) The rollout kernel's block, LDS layout, persistent tile loop and step loop
+// under NodesClosedStep<Launch>: a tile's first step in the launch loads its envs' last
+// observation rows (obs_io) into the observation tile and computes the first action tile from
+// it; after every other step each wave computes its share of the next action tile from the
+// observation tile the step just completed, so between two kept steps nothing crosses HBM but
+// the policy's parameter words (and the outputs asked for, and a sampled launch's noise). The
 // launch's last step leaves obs_io, act_work, reward_sum and the state in HBM.
-// The one-hidden-layer policy (scg_sc_rollout_mlp, csrc/scg_sc_mlp.h) runs the same loops in a
-// kernel of its own, sc_mlp_rollout_nodes_kernel, under NodesMlpStep: where the linear step
-// computes its action tile, every wave first computes its share of the hidden units into a
-// tile over LDS the step leaves idle there (sc_nodes_mlp_act; the note at the end of
-// sc_nodes_tile), so the block's LDS is the linear kernel's. (The step loop is written out in
-// each rollout kernel: moved into a shared inline function it compiled to other code for the
-// linear kernel, whose instruction counts are pinned.)
-struct ScPolicyKArgs {
-  ScArgs a;
-  ScPolicyLaunch p;
-};
-struct ScMlpKArgs {
-  ScArgs a;
-  ScMlpLaunch p;
-};
-
-template <int MAXD, bool F64>
-__global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(kNodesWavesPerEu)))
-void sc_policy_rollout_nodes_kernel(const ScPolicyKArgs k_arg, int W, int E, int K) {
-  const int lane0 = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t n_tiles = (k_arg.a.n + 63) / 64;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    int32_t t = k_arg.a.t;
-    uint32_t episode = k_arg.a.episode;
-    bool keep = false;
-    for (int k = 0; k < K; ++k) {
-      // lane and launch arguments opaque per step, as in the rollout kernel
-      int lane;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane0));
-      typedef const __attribute__((address_space(4))) ScPolicyKArgs* KArgPtr;
-      KArgPtr ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(ap));
-      const ScPolicyKArgs& ka = *(const ScPolicyKArgs*)ap;
-      const ScArgs& a = ka.a;
-      const bool terminal = t == a.c.T;
-      const bool autoreset = terminal && (a.flags & 2);
-      const bool last = k == K - 1;
-      NodesPolicyStep sp{ka.p};
-      sp.t_ = t;
-      sp.flags_ = (terminal ? 1 : 0) | (autoreset ? 2 : 0) | (a.flags & 4);
-      sp.episode_ = episode;
-      sp.k_ = k;
-      sp.keep_ = keep;
-      sp.write_back_ = last || autoreset;
-      sp.last_ = last;
-      sc_nodes_tile<MAXD, F64, false>(a, tile, lane, w, W, E, sp);
-      keep = !autoreset;
-      if (autoreset) {
-        t = 1;
-        ++episode;
-      } else {
-        ++t;
-      }
-    }
-  }
-}
-
-template <int MAXD, bool F64>
-__global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(kNodesWavesPerEu)))
-void sc_mlp_rollout_nodes_kernel(const ScMlpKArgs k_arg, int W, int E, int K) {
-  const int lane0 = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t n_tiles = (k_arg.a.n + 63) / 64;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    int32_t t = k_arg.a.t;
-    uint32_t episode = k_arg.a.episode;
-    bool keep = false;
-    for (int k = 0; k < K; ++k) {
-      // lane and launch arguments opaque per step, as in the rollout kernel
-      int lane;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane0));
-      typedef const __attribute__((address_space(4))) ScMlpKArgs* KArgPtr;
-      KArgPtr ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(ap));
-      const ScMlpKArgs& ka = *(const ScMlpKArgs*)ap;
-      const ScArgs& a = ka.a;
-      const bool terminal = t == a.c.T;
-      const bool autoreset = terminal && (a.flags & 2);
-      const bool last = k == K - 1;
-      NodesMlpStep sp{ka.p};
-      sp.t_ = t;
-      sp.flags_ = (terminal ? 1 : 0) | (autoreset ? 2 : 0) | (a.flags & 4);
-      sp.episode_ = episode;
-      sp.k_ = k;
-      sp.keep_ = keep;
-      sp.write_back_ = last || autoreset;
-      sp.last_ = last;
-      sc_nodes_tile<MAXD, F64, false>(a, tile, lane, w, W, E, sp);
-      keep = !autoreset;
-      if (autoreset) {
-        t = 1;
-        ++episode;
-      } else {
-        ++t;
-      }
-    }
-  }
-}
-
-// The sampled closed loop (scg_sc_rollout_sampled) of either policy: the same loops under
-// NodesClosedStep<ScSampledLaunch<...>>, in kernels of their own, so the deterministic kernels
-// above keep their code.
+// One kernel template, four instantiations per (MAXD, F64), one per launch type: the linear
+// policy or the one-hidden-layer policy, deterministic (ScClosedLaunch) or sampled
+// (ScSampledLaunch). Where the linear step computes its action tile, every wave of an MLP step
+// first computes its share of the hidden units into a tile over LDS the step leaves idle there
+// (sc_nodes_mlp_act; the note at the end of sc_nodes_tile), so the block's LDS is the same for
+// all four; what a launch type does not use (the hidden stage, the noise) is not in its code.
+// The step loop is this kernel's body and, once more, the open-loop rollout kernel's: as the
+// body of a kernel template it compiles for every launch type to the code of a kernel written
+// out for that type alone (instruction counts, registers and scratch compared per
+// instantiation), whereas moved into an inline function that separate kernels
+// call it compiled to other code for the linear kernel. The counter the two loops share (t,
+// episode, keep, the flag word) stays written out in both as well: as a small struct advanced
+// by both loops it left the 24 closed-loop kernels as they were but moved all three open-loop
+// kernels tried (sc_rollout_nodes_kernel<4, true> from 16,867 to 16,718 instructions, <2, false>
+// 13,247 to 13,233, <8, true> 26,609 to 26,605), whose counts are pinned.
 template <class Launch>
-struct ScSampledKArgs {
+struct ScClosedKArgs {
   ScArgs a;
   Launch p;
 };
 
 template <int MAXD, bool F64, class Launch>
 __global__ __launch_bounds__(64 * kNodesMaxWaves) __attribute__((amdgpu_waves_per_eu(kNodesWavesPerEu)))
-void sc_sampled_rollout_nodes_kernel(const ScSampledKArgs<Launch> k_arg, int W, int E, int K) {
+void sc_closed_rollout_nodes_kernel(const ScClosedKArgs<Launch> k_arg, int W, int E, int K) {
   const int lane0 = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t n_tiles = (k_arg.a.n + 63) / 64;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -936,10 +851,10 @@ void sc_sampled_rollout_nodes_kernel(const ScSampledKArgs<Launch> k_arg, int W, 
       // lane and launch arguments opaque per step, as in the rollout kernel
       int lane;
       asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane0));
-      typedef const __attribute__((address_space(4))) ScSampledKArgs<Launch>* KArgPtr;
+      typedef const __attribute__((address_space(4))) ScClosedKArgs<Launch>* KArgPtr;
       KArgPtr ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
       asm volatile("" : "+s"(ap));
-      const ScSampledKArgs<Launch>& ka = *(const ScSampledKArgs<Launch>*)ap;
+      const ScClosedKArgs<Launch>& ka = *(const ScClosedKArgs<Launch>*)ap;
       const ScArgs& a = ka.a;
       const bool terminal = t == a.c.T;
       const bool autoreset = terminal && (a.flags & 2);
@@ -1237,11 +1152,12 @@ int sc_launch_nodes_rollout(const ScArgs& a, int maxd_bucket, int W, int E, int 
   return rc;
 }
 
-// K closed-loop steps of every env in one launch (kKernel: sc_policy_rollout_nodes_kernel or
-// sc_mlp_rollout_nodes_kernel of the launch's policy): the rollout's block, LDS, persistent
-// grid and block cap. a.act is unused; a.obs and a.rew may be null (outputs nobody asked for).
-template <auto kKernel, bool F64, class KArgs, class Launch>
-int sc_launch_nodes_closed_d(const ScArgs& a, const Launch& p, int W, int E, int K, hipStream_t s, const char* name) {
+// K closed-loop steps of every env in one launch (sc_closed_rollout_nodes_kernel of the launch's
+// type): the rollout's block, LDS, persistent grid and block cap. a.act is unused; a.obs and
+// a.rew may be null (outputs nobody asked for).
+template <int MAXD, bool F64, class Launch>
+int sc_launch_nodes_closed_d(const ScArgs& a, const Launch& p, int W, int E, int K, hipStream_t s) {
+  constexpr auto kKernel = &sc_closed_rollout_nodes_kernel<MAXD, F64, Launch>;
   const size_t lds = sc_nodes_lds_bytes(a.c.n_nodes, a.c.P, a.c.H, E, W, a.c.A, a.c.O, F64 ? 8 : 4);
   if (lds > sc_nodes_lds_max()) return fail(SCG_ERR_INVALID, "closed-loop rollout: %zu B of LDS per block", lds);
   int dev = 0;
@@ -1253,65 +1169,38 @@ int sc_launch_nodes_closed_d(const ScArgs& a, const Launch& p, int W, int E, int
   if (resident > 0 && resident < tiles) blocks = resident;
   const int cap = g_nodes_max_blocks.load(std::memory_order_relaxed);
   if (cap > 0 && cap < blocks) blocks = cap;
-  hipLaunchKernelGGL(kKernel, dim3(static_cast<unsigned>(blocks)), dim3(64 * W), lds, s, KArgs{a, p}, W, E, K);
-  return check_launch(name);
+  hipLaunchKernelGGL(kKernel, dim3(static_cast<unsigned>(blocks)), dim3(64 * W), lds, s, ScClosedKArgs<Launch>{a, p}, W, E, K);
+  // the error says which policy, and whether sampled
+  return check_launch(Launch::kMlp ? (Launch::kSampled ? "sc_closed_rollout_nodes_kernel (mlp, sampled)"
+                                                       : "sc_closed_rollout_nodes_kernel (mlp)")
+                                   : (Launch::kSampled ? "sc_closed_rollout_nodes_kernel (linear, sampled)"
+                                                       : "sc_closed_rollout_nodes_kernel (linear)"));
 }
 
+// (scg_sc_nodes_launch.h.) The MLP's hidden tile lies over the inbox values and cost rows of the
+// block's LDS (sc_nodes_tile): a wider one would run into the stocks behind them.
 template <class Launch>
 int sc_launch_nodes_closed(const ScArgs& a, const Launch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
-  constexpr bool kMlp = std::is_same<decltype(Launch::pv), ScMlpView>::value;
+  if constexpr (Launch::kSampled)
+    if (!p.smp.std || !p.smp.noise) return fail(SCG_ERR_INVALID, "sampled closed-loop rollout: std and noise are required");
+  if constexpr (Launch::kMlp)
+    if (p.pv.H < 1 || p.pv.H > sc_mlp_fused_hidden_max(E, a.c.n_nodes))
+      return fail(SCG_ERR_INVALID, "closed-loop rollout: %d hidden units do not fit the block's idle LDS", p.pv.H);
   if (W < 1 || W > kNodesMaxWaves) return fail(SCG_ERR_INVALID, "closed-loop rollout: %d waves per block", W);
   if (a.led_v) return fail(SCG_ERR_INVALID, "closed-loop rollout: no ledgers");
   if (K < 1) return fail(SCG_ERR_INVALID, "closed-loop rollout: steps");
   int rc = SCG_OK;
   const bool found = sc_dispatch_maxd<8>(maxd_bucket, [&](auto d) {
     constexpr int D = decltype(d)::value;
-    constexpr const char* name = Launch::kSampled ? "sc_sampled_rollout_nodes_kernel"
-                                 : kMlp           ? "sc_mlp_rollout_nodes_kernel"
-                                                  : "sc_policy_rollout_nodes_kernel";
-    if constexpr (Launch::kSampled) {
-      using KArgs = ScSampledKArgs<Launch>;
-      rc = a.obs_f64 ? sc_launch_nodes_closed_d<&sc_sampled_rollout_nodes_kernel<D, true, Launch>, true, KArgs>(a, p, W, E, K, s, name)
-                     : sc_launch_nodes_closed_d<&sc_sampled_rollout_nodes_kernel<D, false, Launch>, false, KArgs>(a, p, W, E, K, s, name);
-    } else if constexpr (kMlp) {
-      rc = a.obs_f64 ? sc_launch_nodes_closed_d<&sc_mlp_rollout_nodes_kernel<D, true>, true, ScMlpKArgs>(a, p, W, E, K, s, name)
-                     : sc_launch_nodes_closed_d<&sc_mlp_rollout_nodes_kernel<D, false>, false, ScMlpKArgs>(a, p, W, E, K, s, name);
-    } else {
-      rc = a.obs_f64
-               ? sc_launch_nodes_closed_d<&sc_policy_rollout_nodes_kernel<D, true>, true, ScPolicyKArgs>(a, p, W, E, K, s, name)
-               : sc_launch_nodes_closed_d<&sc_policy_rollout_nodes_kernel<D, false>, false, ScPolicyKArgs>(a, p, W, E, K, s, name);
-    }
+    rc = a.obs_f64 ? sc_launch_nodes_closed_d<D, true>(a, p, W, E, K, s) : sc_launch_nodes_closed_d<D, false>(a, p, W, E, K, s);
   });
   if (!found) return fail(SCG_ERR_INVALID, "closed-loop rollout: nodes ship to at most 8 destinations");
   return rc;
 }
-
-int sc_launch_nodes_policy(const ScArgs& a, const ScPolicyLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
-  return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);
-}
-
-// The hidden tile lies over the inbox values and cost rows of the block's LDS (sc_nodes_tile):
-// a wider one would run into the stocks behind them.
-int sc_launch_nodes_mlp(const ScArgs& a, const ScMlpLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
-  if (p.pv.H < 1 || p.pv.H > sc_mlp_fused_hidden_max(E, a.c.n_nodes))
-    return fail(SCG_ERR_INVALID, "closed-loop rollout: %d hidden units do not fit the block's idle LDS", p.pv.H);
-  return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);
-}
-
-// The sampled launches of both policies (sc_sampled_rollout_nodes_kernel).
-int sc_launch_nodes_policy_sampled(const ScArgs& a, const ScSampledLaunch<ScPolicyView>& p, int maxd_bucket, int W, int E, int K,
-                                   hipStream_t s) {
-  if (!p.smp.std || !p.smp.noise) return fail(SCG_ERR_INVALID, "sampled closed-loop rollout: std and noise are required");
-  return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);
-}
-
-int sc_launch_nodes_mlp_sampled(const ScArgs& a, const ScSampledLaunch<ScMlpView>& p, int maxd_bucket, int W, int E, int K,
-                                hipStream_t s) {
-  if (!p.smp.std || !p.smp.noise) return fail(SCG_ERR_INVALID, "sampled closed-loop rollout: std and noise are required");
-  if (p.pv.H < 1 || p.pv.H > sc_mlp_fused_hidden_max(E, a.c.n_nodes))
-    return fail(SCG_ERR_INVALID, "closed-loop rollout: %d hidden units do not fit the block's idle LDS", p.pv.H);
-  return sc_launch_nodes_closed(a, p, maxd_bucket, W, E, K, s);
-}
+template int sc_launch_nodes_closed(const ScArgs&, const ScClosedLaunch<ScPolicyView>&, int, int, int, int, hipStream_t);
+template int sc_launch_nodes_closed(const ScArgs&, const ScClosedLaunch<ScMlpView>&, int, int, int, int, hipStream_t);
+template int sc_launch_nodes_closed(const ScArgs&, const ScSampledLaunch<ScPolicyView>&, int, int, int, int, hipStream_t);
+template int sc_launch_nodes_closed(const ScArgs&, const ScSampledLaunch<ScMlpView>&, int, int, int, int, hipStream_t);
 
 // The step server's block for a config the batch kernel runs (float64 observations, no
 // ledgers): one block of W waves with the batch kernel's LDS.

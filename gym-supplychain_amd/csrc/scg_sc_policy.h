@@ -44,6 +44,7 @@ SCG_SC_POLICY_HD int sc_policy_word(int O, int a, int j) { return a * (O + 1) + 
 
 // The parameters as the formula reads them: the two strides and the clamp.
 struct ScPolicyView {
+  static constexpr bool kMlp = false;
   const float* params;
   int64_t qstride, nstride;
   float lo, hi;
@@ -114,21 +115,31 @@ struct ScSampleView {
 // Element (k, n, a) of the noise and sample rows.
 SCG_SC_POLICY_HD int64_t sc_sample_index(int64_t N, int A, int64_t k, int64_t n, int a) { return (k * N + n) * A + a; }
 
-// Action a of env n from its observation obs(j), j = 0 .. O-1.
+// The value z_a of env n before its clamp, from the env's observation obs(j), j = 0 .. O-1.
 template <int kChunk, class Obs>
-SCG_SC_POLICY_HD float sc_policy_action(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs) {
+SCG_SC_POLICY_HD float sc_policy_z(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs) {
   const float* row = pv.params + sc_policy_param_index(pv, O, n, a, 0);
-  return sc_policy_clamp(sc_policy_row_sum<kChunk>(row, pv.qstride, O, obs), pv.lo, pv.hi);
+  return sc_policy_row_sum<kChunk>(row, pv.qstride, O, obs);
 }
 
-// The same action sampled: u (stored to *u_out) and its clamp.
+// The two finishes of a z, the linear policy's or the MLP's (scg_sc_mlp.h sc_mlp_z): the action
+// is sc_policy_clamp(z, lo, hi), or sampled the clamp of u, which goes to *u_out.
+SCG_SC_POLICY_HD float sc_policy_clamp_sampled(float z, float std, float eps, float lo, float hi, float* u_out) {
+  const float u = sc_policy_sample(z, std, eps);
+  *u_out = u;
+  return sc_policy_clamp(u, lo, hi);
+}
+
+// Action a of env n in one call, deterministic and sampled (u to *u_out): sc_policy_z under its
+// two finishes, for callers with nothing to do between the two.
+template <int kChunk, class Obs>
+SCG_SC_POLICY_HD float sc_policy_action(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs) {
+  return sc_policy_clamp(sc_policy_z<kChunk>(pv, O, n, a, obs), pv.lo, pv.hi);
+}
 template <int kChunk, class Obs>
 SCG_SC_POLICY_HD float sc_policy_action_sampled(const ScPolicyView& pv, int O, int64_t n, int a, const Obs& obs, float std,
                                                 float eps, float* u_out) {
-  const float* row = pv.params + sc_policy_param_index(pv, O, n, a, 0);
-  const float u = sc_policy_sample(sc_policy_row_sum<kChunk>(row, pv.qstride, O, obs), std, eps);
-  *u_out = u;
-  return sc_policy_clamp(u, pv.lo, pv.hi);
+  return sc_policy_clamp_sampled(sc_policy_z<kChunk>(pv, O, n, a, obs), std, eps, pv.lo, pv.hi, u_out);
 }
 
 // What a closed-loop launch takes beside the step's launch arguments (scg_sc_nodes.hip), for
@@ -136,6 +147,7 @@ SCG_SC_POLICY_HD float sc_policy_action_sampled(const ScPolicyView& pv, int O, i
 template <class View>
 struct ScClosedLaunch {
   static constexpr bool kSampled = false;
+  static constexpr bool kMlp = View::kMlp;
   View pv;
   void* obs_io;         // [N][O], obs dtype: read at the launch's first step, written at its last
   float* act_work;      // [N][A]: the launch's last action rows
@@ -143,19 +155,14 @@ struct ScClosedLaunch {
   double* reward_sum;   // [N]
   int32_t sum_add;      // 0: the launch stores its rewards' sum; else it adds to what is there
 };
-using ScPolicyLaunch = ScClosedLaunch<ScPolicyView>;
 
-// A sampled closed-loop launch: the same, and the launch's noise.
+// A sampled closed-loop launch: the same, and behind it the launch's noise.
 template <class View>
-struct ScSampledLaunch {
+struct ScSampledLaunch : ScClosedLaunch<View> {
   static constexpr bool kSampled = true;
-  View pv;
-  void* obs_io;
-  float* act_work;
-  float* actions_out;
-  double* reward_sum;
-  int32_t sum_add;
   ScSampleView smp;
 };
+static_assert(sizeof(ScSampledLaunch<ScPolicyView>) == sizeof(ScClosedLaunch<ScPolicyView>) + sizeof(ScSampleView),
+              "the kernel arguments: smp directly behind the common fields");
 
 }  // namespace scg

@@ -4,8 +4,8 @@
 // observation rows, deterministic or with the caller's noise added before the clamp
 // (csrc/scg_sc_policy.h, csrc/scg_sc_mlp.h: the one definition of each formula), and the entry
 // points, one host body for both policies, which runs either the fused kernel (scg_sc_nodes.hip
-// sc_policy_rollout_nodes_kernel, sc_mlp_rollout_nodes_kernel) or, for every other case, the
-// action kernel and scg_sc_step per step.
+// sc_closed_rollout_nodes_kernel) or, for every other case, the action kernel and scg_sc_step
+// per step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,8 +13,7 @@
 #include "scg_common.h"
 #include "scg_supplychain_core.h"
 #include "scg_supplychain_args.h"
-#include "scg_sc_policy.h"
-#include "scg_sc_mlp.h"
+#include "scg_sc_nodes_launch.h"
 
 namespace scg {
 
@@ -22,13 +21,6 @@ namespace scg {
 int sc_host_check(const scg_sc_config* cfg, const scg_sc_state* st);
 ScArgs sc_host_args(const scg_sc_config* cfg, const scg_sc_state* st);
 int sc_rollout_chunk_steps();
-// scg_sc_nodes.hip
-int sc_launch_nodes_policy(const ScArgs& a, const ScPolicyLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s);
-int sc_launch_nodes_mlp(const ScArgs& a, const ScMlpLaunch& p, int maxd_bucket, int W, int E, int K, hipStream_t s);
-int sc_launch_nodes_policy_sampled(const ScArgs& a, const ScSampledLaunch<ScPolicyView>& p, int maxd_bucket, int W, int E, int K,
-                                   hipStream_t s);
-int sc_launch_nodes_mlp_sampled(const ScArgs& a, const ScSampledLaunch<ScMlpView>& p, int maxd_bucket, int W, int E, int K,
-                                hipStream_t s);
 
 // sc_reset_kernel's addressing without the reset: env n's observation at a.t of a.episode.
 __global__ __launch_bounds__(kScBlock) void sc_observe_kernel(const ScArgs a) {
@@ -39,51 +31,60 @@ __global__ __launch_bounds__(kScBlock) void sc_observe_kernel(const ScArgs a) {
   sc_observe(a.c, e, a.t, out);
 }
 
+// f(o), for o(j) the float32 of element j of row n of obs [N][O], float64 or float32. (The
+// callers' f capture the thread's indices by value: captured by reference they compiled to
+// other code for the four action kernels, whose instruction counts are pinned.)
+template <class F>
+__device__ __forceinline__ auto sc_with_obs_row(const void* obs, int obs_f64, int64_t n, int O, const F& f) {
+  if (obs_f64) {
+    const double* row = static_cast<const double*>(obs) + n * O;
+    return f([&](int j) { return static_cast<float>(row[j]); });
+  } else {
+    const float* row = static_cast<const float*>(obs) + n * O;
+    return f([&](int j) { return row[j]; });
+  }
+}
+
 // Action q of env n, thread q * N + n (env fastest: a wave reads each parameter word of its
 // envs as one row), from row n of obs [N][O] into row n of out0 and, when given, out1 [N][A].
+// kSampled (scg_sc_rollout_sampled): smp.noise and, when given, smp.samples are the step's rows
+// [N][A] of the call's noise and samples_out; a thread reads its element of the one and then
+// writes the same element of the other, so the two may be one buffer.
 constexpr int kPolicyActBlock = 256;
 constexpr int kPolicyActChunk = 16;
-__global__ __launch_bounds__(kPolicyActBlock) void sc_policy_act_kernel(const ScPolicyView pv, const void* obs, int obs_f64,
-                                                                         int64_t N, int A, int O, float* out0, float* out1) {
+template <bool kSampled>
+__device__ __forceinline__ void sc_policy_act(const ScPolicyView& pv, const void* obs, int obs_f64, int64_t N, int A, int O,
+                                              float* out0, float* out1, const ScSampleView& smp) {
   const int64_t id = static_cast<int64_t>(blockIdx.x) * kPolicyActBlock + threadIdx.x;
   if (id >= N * A) return;
   const int q = static_cast<int>(id / N);
   const int64_t n = id - static_cast<int64_t>(q) * N;
-  float act;
-  if (obs_f64) {
-    const double* row = static_cast<const double*>(obs) + n * O;
-    act = sc_policy_action<kPolicyActChunk>(pv, O, n, q, [&](int j) { return static_cast<float>(row[j]); });
-  } else {
-    const float* row = static_cast<const float*>(obs) + n * O;
-    act = sc_policy_action<kPolicyActChunk>(pv, O, n, q, [&](int j) { return row[j]; });
-  }
+  [[maybe_unused]] float sd, e, u;  // the sampled body's alone: set and read only under kSampled
+  if constexpr (kSampled) sd = smp.std[q], e = smp.noise[n * A + q];
+  float* const u_out = &u;
+  const float act = sc_with_obs_row(obs, obs_f64, n, O, [=, &pv](auto o) {
+    if constexpr (kSampled) {
+      return sc_policy_action_sampled<kPolicyActChunk>(pv, O, n, q, o, sd, e, u_out);
+    } else {
+      return sc_policy_action<kPolicyActChunk>(pv, O, n, q, o);
+    }
+  });
   out0[n * A + q] = act;
   if (out1) out1[n * A + q] = act;
+  if constexpr (kSampled)
+    if (smp.samples) smp.samples[n * A + q] = u;
 }
 
-// The same with sampled actions (scg_sc_rollout_sampled): eps and, when given, samples are the
-// step's rows [N][A] of the call's noise and samples_out; a thread reads its element of the one
-// and then writes the same element of the other, so the two may be one buffer.
+// The two kernels of it: the deterministic one takes no noise arguments.
+__global__ __launch_bounds__(kPolicyActBlock) void sc_policy_act_kernel(const ScPolicyView pv, const void* obs, int obs_f64,
+                                                                         int64_t N, int A, int O, float* out0, float* out1) {
+  sc_policy_act<false>(pv, obs, obs_f64, N, A, O, out0, out1, ScSampleView{});
+}
 __global__ __launch_bounds__(kPolicyActBlock) void sc_policy_act_sampled_kernel(const ScPolicyView pv, const void* obs,
                                                                                  int obs_f64, int64_t N, int A, int O,
                                                                                  float* out0, float* out1, const float* std,
                                                                                  const float* eps, float* samples) {
-  const int64_t id = static_cast<int64_t>(blockIdx.x) * kPolicyActBlock + threadIdx.x;
-  if (id >= N * A) return;
-  const int q = static_cast<int>(id / N);
-  const int64_t n = id - static_cast<int64_t>(q) * N;
-  const float sd = std[q], e = eps[n * A + q];
-  float act, u;
-  if (obs_f64) {
-    const double* row = static_cast<const double*>(obs) + n * O;
-    act = sc_policy_action_sampled<kPolicyActChunk>(pv, O, n, q, [&](int j) { return static_cast<float>(row[j]); }, sd, e, &u);
-  } else {
-    const float* row = static_cast<const float*>(obs) + n * O;
-    act = sc_policy_action_sampled<kPolicyActChunk>(pv, O, n, q, [&](int j) { return row[j]; }, sd, e, &u);
-  }
-  out0[n * A + q] = act;
-  if (out1) out1[n * A + q] = act;
-  if (samples) samples[n * A + q] = u;
+  sc_policy_act<true>(pv, obs, obs_f64, N, A, O, out0, out1, ScSampleView{std, eps, samples});
 }
 
 // sum = (add ? sum : 0.0) + r: the per-step path's reward_sum.
@@ -102,56 +103,42 @@ __global__ __launch_bounds__(kPolicyActBlock) void sc_reward_sum_kernel(double* 
 // writes its own column only: no barrier. Per-env parameter words are read as 256-byte rows.
 constexpr int kMlpActBlock = 64;
 constexpr int kMlpActChunk = 16;
-// (Four waves per SIMD: at most 128 VGPRs, as the node-parallel kernels.)
-__global__ __launch_bounds__(kMlpActBlock) __attribute__((amdgpu_waves_per_eu(4)))
-void sc_mlp_act_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1) {
+// kSampled: smp as sc_policy_act's, the env's row read and written by the env's thread.
+template <bool kSampled>
+__device__ __forceinline__ void sc_mlp_act(const ScMlpView& mv, const void* obs, int obs_f64, int64_t N, int A, int O,
+                                           float* out0, float* out1, const ScSampleView& smp) {
   extern __shared__ float hid_t[];  // [H][64]
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kMlpActBlock + threadIdx.x;
   if (n >= N) return;
   float* const hid = hid_t + threadIdx.x;
-  if (obs_f64) {
-    const double* row = static_cast<const double*>(obs) + n * O;
-    auto o = [&](int j) { return static_cast<float>(row[j]); };
+  sc_with_obs_row(obs, obs_f64, n, O, [=, &mv](auto o) {
     for (int i = 0; i < mv.H; ++i) hid[i * kMlpActBlock] = sc_mlp_hidden<kMlpActChunk>(mv, O, n, i, o);
-  } else {
-    const float* row = static_cast<const float*>(obs) + n * O;
-    auto o = [&](int j) { return row[j]; };
-    for (int i = 0; i < mv.H; ++i) hid[i * kMlpActBlock] = sc_mlp_hidden<kMlpActChunk>(mv, O, n, i, o);
-  }
+  });
   auto h = [&](int i) { return hid[i * kMlpActBlock]; };
   for (int q = 0; q < A; ++q) {
-    const float act = sc_mlp_action<kMlpActChunk>(mv, O, n, q, h);
+    [[maybe_unused]] float u;
+    float act;
+    if constexpr (kSampled) {
+      act = sc_mlp_action_sampled<kMlpActChunk>(mv, O, n, q, h, smp.std[q], smp.noise[n * A + q], &u);
+    } else {
+      act = sc_mlp_action<kMlpActChunk>(mv, O, n, q, h);
+    }
     out0[n * A + q] = act;
     if (out1) out1[n * A + q] = act;
+    if constexpr (kSampled)
+      if (smp.samples) smp.samples[n * A + q] = u;
   }
 }
 
-// The same with sampled actions: eps / samples as sc_policy_act_sampled_kernel's, the env's row
-// read and written by the env's thread.
+// The two kernels of it. (Four waves per SIMD: at most 128 VGPRs, as the node-parallel kernels.)
+__global__ __launch_bounds__(kMlpActBlock) __attribute__((amdgpu_waves_per_eu(4)))
+void sc_mlp_act_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1) {
+  sc_mlp_act<false>(mv, obs, obs_f64, N, A, O, out0, out1, ScSampleView{});
+}
 __global__ __launch_bounds__(kMlpActBlock) __attribute__((amdgpu_waves_per_eu(4)))
 void sc_mlp_act_sampled_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0,
                                float* out1, const float* std, const float* eps, float* samples) {
-  extern __shared__ float hid_t[];  // [H][64]
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kMlpActBlock + threadIdx.x;
-  if (n >= N) return;
-  float* const hid = hid_t + threadIdx.x;
-  if (obs_f64) {
-    const double* row = static_cast<const double*>(obs) + n * O;
-    auto o = [&](int j) { return static_cast<float>(row[j]); };
-    for (int i = 0; i < mv.H; ++i) hid[i * kMlpActBlock] = sc_mlp_hidden<kMlpActChunk>(mv, O, n, i, o);
-  } else {
-    const float* row = static_cast<const float*>(obs) + n * O;
-    auto o = [&](int j) { return row[j]; };
-    for (int i = 0; i < mv.H; ++i) hid[i * kMlpActBlock] = sc_mlp_hidden<kMlpActChunk>(mv, O, n, i, o);
-  }
-  auto h = [&](int i) { return hid[i * kMlpActBlock]; };
-  for (int q = 0; q < A; ++q) {
-    float u;
-    const float act = sc_mlp_action_sampled<kMlpActChunk>(mv, O, n, q, h, std[q], eps[n * A + q], &u);
-    out0[n * A + q] = act;
-    if (out1) out1[n * A + q] = act;
-    if (samples) samples[n * A + q] = u;
-  }
+  sc_mlp_act<true>(mv, obs, obs_f64, N, A, O, out0, out1, ScSampleView{std, eps, samples});
 }
 
 // Whether hidden units fit the LDS the fused kernel has idle for them (a config scg_sc_prepare
@@ -161,8 +148,8 @@ bool sc_mlp_fits(const scg_sc_config* cfg, int32_t hidden) {
 }
 
 // What the closed loop's host body needs of a policy: its argument check, whether it fuses
-// beyond the linear condition, and its launches: the action rows of one step (smp: the step's
-// rows of a sampled call's noise, or null) and the fused launch, deterministic or sampled.
+// beyond the linear condition, its view for the fused launch (sc_launch_nodes_closed) and the
+// launch of the action rows of one step (smp: the step's rows of a sampled call's noise, or null).
 struct LinearHost {
   const scg_sc_policy* pol;
   int check() const {
@@ -183,12 +170,6 @@ struct LinearHost {
     }
     hipLaunchKernelGGL(sc_policy_act_kernel, grid, dim3(kPolicyActBlock), 0, s, pv, obs, obs_f64, N, A, O, out0, out1);
     return check_launch("sc_policy_act_kernel");
-  }
-  static int fused(const ScArgs& a, const ScPolicyLaunch& p, int maxd, int W, int E, int K, hipStream_t s) {
-    return sc_launch_nodes_policy(a, p, maxd, W, E, K, s);
-  }
-  static int fused(const ScArgs& a, const ScSampledLaunch<ScPolicyView>& p, int maxd, int W, int E, int K, hipStream_t s) {
-    return sc_launch_nodes_policy_sampled(a, p, maxd, W, E, K, s);
   }
 };
 
@@ -217,12 +198,6 @@ struct MlpHost {
     }
     hipLaunchKernelGGL(sc_mlp_act_kernel, grid, dim3(kMlpActBlock), lds, s, mv, obs, obs_f64, N, A, O, out0, out1);
     return check_launch("sc_mlp_act_kernel");
-  }
-  static int fused(const ScArgs& a, const ScMlpLaunch& p, int maxd, int W, int E, int K, hipStream_t s) {
-    return sc_launch_nodes_mlp(a, p, maxd, W, E, K, s);
-  }
-  static int fused(const ScArgs& a, const ScSampledLaunch<ScMlpView>& p, int maxd, int W, int E, int K, hipStream_t s) {
-    return sc_launch_nodes_mlp_sampled(a, p, maxd, W, E, K, s);
   }
 };
 
@@ -312,16 +287,11 @@ int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_step
     a.t = st->time_step + 1;
     a.flags = (reset ? 2 : 0) | ((flags & SCG_SC_SERIAL) ? 4 : 0);
     float* const arows = actions_out ? actions_out + static_cast<int64_t>(k0) * N * A : nullptr;
-    const int32_t sum_add = k0 > 0 ? 1 : 0;
-    int rc;
-    if (smp) {
-      const ScSampledLaunch<decltype(pv)> p{pv, obs_io, act_work, arows, reward_sum, sum_add, rows(k0)};
-      rc = Policy::fused(a, p, maxd, cfg->group, cfg->inbox_size, kc, s);
-    } else {
-      const ScClosedLaunch<decltype(pv)> p{pv, obs_io, act_work, arows, reward_sum, sum_add};
-      rc = Policy::fused(a, p, maxd, cfg->group, cfg->inbox_size, kc, s);
-    }
-    if (rc) return rc;
+    const ScClosedLaunch<decltype(pv)> p{pv, obs_io, act_work, arows, reward_sum, k0 > 0 ? 1 : 0};
+    const int W = cfg->group, E = cfg->inbox_size;
+    if (int rc = smp ? sc_launch_nodes_closed(a, ScSampledLaunch<decltype(pv)>{p, rows(k0)}, maxd, W, E, kc, s)
+                     : sc_launch_nodes_closed(a, p, maxd, W, E, kc, s))
+      return rc;
     const int64_t end = static_cast<int64_t>(st->time_step) + kc;  // <= T without auto-reset
     if (reset) {
       crossed += static_cast<int32_t>(end / T);

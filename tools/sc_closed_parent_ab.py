@@ -12,7 +12,10 @@ episodes of `--steps` steps between two device synchronisations:
   rollout          rollout(steps) of fixed actions, last observation only;
   linear_per_env   rollout_policy(steps) with a linear policy per env;
   linear_shared    the same with one shared policy;
-  mlp_per_env      rollout_policy(steps) with a 16-unit MLP per env.
+  mlp_per_env      rollout_policy(steps) with a 16-unit MLP per env;
+  linear_sampled   linear_per_env with sampled actions: noise [steps, N, A] drawn once, std 0.1,
+                   no samples_out;
+  mlp_sampled      mlp_per_env with the same noise and std.
 A process reports the median of its three samples per path, in microseconds per step of the
 batch. The summary gives, per path and build, the median, minimum and maximum of the rounds'
 figures, and whether this tree's median lies inside the other build's minimum .. maximum, else
@@ -27,7 +30,7 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PATHS = ("rollout", "linear_per_env", "linear_shared", "mlp_per_env")
+PATHS = ("rollout", "linear_per_env", "linear_shared", "mlp_per_env", "linear_sampled", "mlp_sampled")
 SEED = 0x5EED0000
 
 
@@ -53,6 +56,8 @@ def child(a):
     W, b = rnd((N, A, O), 0.1), rnd((N, A), 0.3)
     packed = {"linear_per_env": e.pack_policy(W, b), "linear_shared": e.pack_policy(W[0], b[0]),
               "mlp_per_env": e.pack_mlp(rnd((N, H, O), 0.1), rnd((N, H), 0.3), rnd((N, A, H), 0.3), rnd((N, A), 0.3))}
+    packed["linear_sampled"], packed["mlp_sampled"] = packed["linear_per_env"], packed["mlp_per_env"]
+    noise = torch.randn((T, N, A), generator=torch.Generator(device=dev).manual_seed(SEED + 1), device=dev)
     acts = torch.rand((T, N, A), generator=torch.Generator(device=dev).manual_seed(SEED), device=dev) * 2 - 1
     last = torch.empty((N, O), dtype=torch.float32, device=dev)
     rew = torch.empty((T, N), dtype=torch.float64, device=dev)
@@ -60,6 +65,8 @@ def child(a):
     def run(name):
         if name == "rollout":
             envs[name].rollout(acts, last, rew, last_obs_only=True)
+        elif name.endswith("_sampled"):
+            envs[name].rollout_policy(packed[name], None, T, noise=noise, std=0.1)
         else:
             envs[name].rollout_policy(packed[name], None, T)
 
