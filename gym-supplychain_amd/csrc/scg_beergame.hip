@@ -601,38 +601,54 @@ int scg_bg_server_step(const scg_bg_config* cfg, scg_bg_state* st, scg_bg_server
   return scg_bg_server_wait(st, slot, -1, done);
 }
 
-int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const int32_t* actions,
-                   int32_t* obs, int32_t* rewards, uint32_t flags, void* stream) {
-  if (int rc = check_state(cfg, st)) return rc;
-  if (!actions || n_weeks < 0) return fail(SCG_ERR_INVALID, "rollout needs actions and n_weeks >= 0");
-  if (int rc = check_step(cfg, st)) return rc;
+// ---- rollouts ---------------------------------------------------------------------------
+static int check_horizon(const scg_bg_config* cfg, const scg_bg_state* st, int32_t n_weeks, uint32_t flags) {
   if (!(flags & SCG_BG_AUTORESET) && st->week + static_cast<int64_t>(n_weeks) > cfg->max_weeks)
     return fail(SCG_ERR_PAST_HORIZON, "rollout of %d weeks from week %d passes the terminal week %d", n_weeks,
                 st->week, cfg->max_weeks);
-  const int64_t stride = st->n_envs * cfg->levels;
+  return SCG_OK;
+}
+
+// A call of n_weeks as launches of up to SCG_BG_ROLLOUT_MAX weeks: launch(done_k, K, args, weeks)
+// runs weeks done_k .. done_k + K of the call; the state's week and episode follow each launch.
+extern "C++" {
+template <class Launch>
+static int rollout_launches(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, uint32_t flags,
+                            Launch&& launch) {
   int32_t done_k = 0;
   while (done_k < n_weeks) {
-    // one launch covers up to SCG_BG_ROLLOUT_MAX weeks; without auto-reset it stops at T
     RolloutWeeks weeks;
     int32_t K = 0;
     scg_bg_state probe = *st;
-    BgArgs a = make_args(cfg, st);
+    const BgArgs a = make_args(cfg, st);
     while (K < SCG_BG_ROLLOUT_MAX && done_k + K < n_weeks) {
       weeks.wk[K] = week_info(cfg, probe.week + 1, flags);
       advance_week(&probe, weeks.wk[K]);
       ++K;
     }
-    if (int rc = with_level(cfg->levels, [&](const BgLaunchers& k) {
-          const auto launch = cfg->variant == 2 ? k.rollout2 : k.rollout;
-          return launch(grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, K, weeks, actions + done_k * stride,
-                        obs ? obs + done_k * stride : nullptr, rewards ? rewards + done_k * st->n_envs : nullptr);
-        }))
-      return rc;
+    if (int rc = launch(done_k, K, a, weeks)) return rc;
     st->week = probe.week;
     st->episode = probe.episode;
     done_k += K;
   }
   return SCG_OK;
+}
+}  // extern "C++"
+
+int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const int32_t* actions,
+                   int32_t* obs, int32_t* rewards, uint32_t flags, void* stream) {
+  if (int rc = check_state(cfg, st)) return rc;
+  if (!actions || n_weeks < 0) return fail(SCG_ERR_INVALID, "rollout needs actions and n_weeks >= 0");
+  if (int rc = check_step(cfg, st)) return rc;
+  if (int rc = check_horizon(cfg, st, n_weeks, flags)) return rc;
+  const int64_t stride = st->n_envs * cfg->levels;
+  return rollout_launches(cfg, st, n_weeks, flags, [&](int32_t done_k, int32_t K, const BgArgs& a, const RolloutWeeks& weeks) {
+    const RolloutActs src{actions + done_k * stride, obs ? obs + done_k * stride : nullptr,
+                          rewards ? rewards + done_k * st->n_envs : nullptr};
+    return with_level(cfg->levels, [&](const BgLaunchers& k) {
+      return k.rollout(cfg->variant, grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, K, weeks, src);
+    });
+  });
 }
 
 int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_policy* policy,
@@ -648,9 +664,7 @@ int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_
     return fail(SCG_ERR_INVALID, "policy rollout: levels=%d above %d", cfg->levels, SCG_BG_POLICY_MAX_LEVELS);
   if (n_weeks < 0) return fail(SCG_ERR_INVALID, "policy rollout needs n_weeks >= 0");
   if (int rc = check_step(cfg, st)) return rc;
-  if (!(flags & SCG_BG_AUTORESET) && st->week + static_cast<int64_t>(n_weeks) > cfg->max_weeks)
-    return fail(SCG_ERR_PAST_HORIZON, "rollout of %d weeks from week %d passes the terminal week %d", n_weeks,
-                st->week, cfg->max_weeks);
+  if (int rc = check_horizon(cfg, st, n_weeks, flags)) return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
   if (n_weeks == 0) {  // no launch: the sum of no rewards
     if (reward_sum && hipMemsetAsync(reward_sum, 0, static_cast<size_t>(st->n_envs) * sizeof(int64_t), s) != hipSuccess)
@@ -658,17 +672,7 @@ int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_
     return SCG_OK;
   }
   const int64_t stride = st->n_envs * cfg->levels;
-  int32_t done_k = 0;
-  while (done_k < n_weeks) {  // launches of up to SCG_BG_ROLLOUT_MAX weeks, as scg_bg_rollout cuts them
-    RolloutWeeks weeks;
-    int32_t K = 0;
-    scg_bg_state probe = *st;
-    const BgArgs a = make_args(cfg, st);
-    while (K < SCG_BG_ROLLOUT_MAX && done_k + K < n_weeks) {
-      weeks.wk[K] = week_info(cfg, probe.week + 1, flags);
-      advance_week(&probe, weeks.wk[K]);
-      ++K;
-    }
+  return rollout_launches(cfg, st, n_weeks, flags, [&](int32_t done_k, int32_t K, const BgArgs& a, const RolloutWeeks& weeks) {
     PolicyArgs pa;
     pa.params = policy->params;
     pa.acts_out = actions_out ? actions_out + done_k * stride : nullptr;
@@ -677,12 +681,8 @@ int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_
     pa.reward_sum = reward_sum;
     pa.clamp = PolicyClamp{policy->shift, policy->act_lo, policy->act_hi};
     pa.first = done_k == 0;
-    if (int rc = bg_launch_policy_rollout(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, pa)) return rc;
-    st->week = probe.week;
-    st->episode = probe.episode;
-    done_k += K;
-  }
-  return SCG_OK;
+    return bg_launch_policy_rollout(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, pa);
+  });
 }
 
 int scg_bg_poisson_demand(const scg_bg_config* cfg, const scg_bg_state* st, uint32_t episode, int32_t* out,

@@ -939,129 +939,9 @@ struct RingLds {
   }
 };
 
-// K weeks per launch, inventory/backlog/orders/ledgers/return in registers; per week only
-// the action row in and the obs/reward (and history) rows out touch HBM. With LDS the
-// pipeline ring is staged in shared memory for the whole launch (loaded once, stored
-// once); otherwise its rows are read-modify-written through L2.
-// Weeks run in groups of kRolloutGroup: the group's action rows are all requested before
-// its first week, so a launch waits on memory once per group instead of once per week.
-constexpr int kRolloutGroup = 8;
-
-template <int L, class Ring>
-__device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t K, const RolloutWeeks& weeks,
-                                             const int32_t* __restrict__ acts, int32_t* __restrict__ obs_out,
-                                             int32_t* __restrict__ rew_out, const Ring& ring) {
-  const int64_t row = n * L;
-  const int64_t stride = a.n * L;
-  int32_t inv[L], bk[L], op[L], iacc[L], bacc[L];
-  load_row<L>(a.inv + row, inv);
-  load_row<L>(a.bk + row, bk);
-  load_row<L>(a.op + row, op);
-  zero_row<L>(iacc);
-  zero_row<L>(bacc);
-  if (a.inv_acc) load_row<L>(a.inv_acc + row, iacc);
-  if (a.bk_acc) load_row<L>(a.bk_acc + row, bacc);
-  int64_t ret = a.ep_ret ? a.ep_ret[n] : 0;
-  uint32_t episode = a.episode;
-  bool ovf = false;
-  for (int32_t k0 = 0; k0 < K; k0 += kRolloutGroup) {
-  int32_t group_act[kRolloutGroup][L];
-#pragma unroll
-  for (int u = 0; u < kRolloutGroup; ++u)
-    if (k0 + u < K) load_row<L>(acts + (k0 + u) * stride + row, group_act[u]);
-#pragma unroll
-  for (int u = 0; u < kRolloutGroup; ++u) {
-    const int32_t k = k0 + u;
-    if (k >= K) break;
-    const WeekInfo wk = weeks.wk[k];
-    int32_t due[L], obs[L], ship[L], cur[L];
-    int32_t(&act)[L] = group_act[u];
-    zero_row<L>(due);
-    if (wk.read_slot >= 0) ring.load(wk.read_slot, due);
-    int32_t demand;
-    if (a.demand_mode == SCG_DEMAND_FIXED)
-      demand = wk.demand_fixed;
-    else
-      demand = week_demand(a, n, wk.week, episode);
-    zero_row<L>(cur);
-    if (wk.mode == MODE_ADD) ring.load(wk.write_slot, cur);
-    const int32_t reward = week_update<L>(a.h, a.b, a.guard, demand, wk.mode == MODE_DIRECT, due, inv, bk, op, act, ship,
-                                          obs, cur, iacc, bacc, ovf);
-    if (wk.mode == MODE_STORE) {
-      ring.store(wk.write_slot, ship);
-    } else if (wk.mode == MODE_ADD) {
-      ring.store(wk.write_slot, cur);
-    }
-    if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
-    ret += reward;
-    if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
-    if (wk.flags & WEEK_AUTORESET) {  // auto-reset in registers (:140-156)
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        inv[l] = a.init_inv[l];
-        bk[l] = 0;
-        op[l] = a.orders_value;
-        iacc[l] = bacc[l] = 0;
-        obs[l] = inv[l];
-      }
-      int32_t init[L];
-#pragma unroll
-      for (int l = 0; l < L; ++l) init[l] = a.ship_value;
-      for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, init);
-      if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
-      ret = 0;
-      ++episode;
-    }
-    if (obs_out) store_row<L>(obs_out + k * stride + row, obs);
-    if (rew_out) rew_out[k * a.n + n] = reward;
-  }
-  }
-  store_row<L>(a.inv + row, inv);
-  store_row<L>(a.bk + row, bk);
-  store_row<L>(a.op + row, op);
-  if (a.inv_acc) store_row<L>(a.inv_acc + row, iacc);
-  if (a.bk_acc) store_row<L>(a.bk_acc + row, bacc);
-  if (a.ep_ret) a.ep_ret[n] = ret;
-  note_overflow(a.err, ovf);
-}
-
-template <int L>
-__global__ __launch_bounds__(kBlock) void bg_rollout_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
-                                                            const int32_t* __restrict__ acts, int32_t* __restrict__ obs_out,
-                                                            int32_t* __restrict__ rew_out) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (n >= a.n) return;
-  rollout_body<L>(a, n, K, weeks, acts, obs_out, rew_out, RingHbm<L>{a.ring, a.n * L, n * L});
-}
-
-template <int L>
-__global__ __launch_bounds__(kBlock) void bg_rollout_lds_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
-                                                                const int32_t* __restrict__ acts,
-                                                                int32_t* __restrict__ obs_out,
-                                                                int32_t* __restrict__ rew_out) {
-  extern __shared__ int32_t lds_ring[];
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (n >= a.n) return;  // lanes only touch their own LDS column: no block barrier needed
-  const RingHbm<L> hbm{a.ring, a.n * L, n * L};
-  const RingLds<L> lds{lds_ring + threadIdx.x};
-  for (int s = 0; s < a.ring_slots; ++s) {
-    int32_t v[L];
-    hbm.load(s, v);
-    lds.store(s, v);
-  }
-  rollout_body<L>(a, n, K, weeks, acts, obs_out, rew_out, lds);
-  for (int s = 0; s < a.ring_slots; ++s) {
-    int32_t v[L];
-    lds.load(s, v);
-    hbm.store(s, v);
-  }
-}
-
-// ---- BeerGameEnv2 rollout ---------------------------------------------------------------
 // One BeerGameEnv2 week of one env in registers: the arithmetic of bg2_step_kernel, statement
 // for statement (int64 as the reference computes it, every stored value checked against
-// int32). A second copy on purpose: bg2_step_kernel keeps its own body, so its generated code
-// stays what it was (DESIGN §6.1 on what a shared body cost the slab kernel's schedule).
+// int32); bg2_step_kernel keeps its own body.
 template <int L>
 __device__ __forceinline__ int32_t week2_update(const BgArgs& a, int32_t demand, bool direct, const int32_t (&due)[L],
                                                 int32_t (&inv)[L], int32_t (&bk)[L], int32_t (&op)[L],
@@ -1107,159 +987,32 @@ __device__ __forceinline__ int32_t week2_update(const BgArgs& a, int32_t demand,
   return static_cast<int32_t>(reward64);
 }
 
-// K BeerGameEnv2 weeks per launch: inventory, backlog, orders, the three ledgers and the
-// return stay in registers; per week the action row comes in and the obs / reward (and
-// history) rows go out, 36 B per env-week at L = 4, and everything else is written once at
-// the end. With a delay list the host's weeks give the ring slots and modes, as in
-// rollout_body; with stochastic delays each lane draws its own week's delay under the
-// in-register episode, clears the slot it received and read-modify-writes the slot it ships
-// into, so slots differ between lanes: both ring views take a per-lane slot (in LDS a lane
-// only ever touches its own column, whatever the slot).
-// An auto-reset inside the launch is reset_env on the ring view and the registers.
-template <int L, class Ring>
-__device__ __forceinline__ void rollout2_body(const BgArgs& a, int64_t n, int32_t K, const RolloutWeeks& weeks,
-                                              const int32_t* __restrict__ acts, int32_t* __restrict__ obs_out,
-                                              int32_t* __restrict__ rew_out, const Ring& ring) {
-  const int64_t row = n * L;
-  const int64_t stride = a.n * L;
-  int32_t inv[L], bk[L], op[L], iacc[L], bacc[L], pacc[L];
-  load_row<L>(a.inv + row, inv);
-  load_row<L>(a.bk + row, bk);
-  load_row<L>(a.op + row, op);
-  zero_row<L>(iacc);
-  zero_row<L>(bacc);
-  zero_row<L>(pacc);
-  if (a.inv_acc) load_row<L>(a.inv_acc + row, iacc);
-  if (a.bk_acc) load_row<L>(a.bk_acc + row, bacc);
-  if (a.pen_acc) load_row<L>(a.pen_acc + row, pacc);
-  int64_t ret = a.ep_ret ? a.ep_ret[n] : 0;
-  uint32_t episode = a.episode;
-  bool ovf = false;
-  for (int32_t k0 = 0; k0 < K; k0 += kRolloutGroup) {
-  int32_t group_act[kRolloutGroup][L];
-#pragma unroll
-  for (int u = 0; u < kRolloutGroup; ++u)
-    if (k0 + u < K) load_row<L>(acts + (k0 + u) * stride + row, group_act[u]);
-#pragma unroll
-  for (int u = 0; u < kRolloutGroup; ++u) {
-    const int32_t k = k0 + u;
-    if (k >= K) break;
-    const WeekInfo wk = weeks.wk[k];
-    const bool autoreset = wk.flags & WEEK_AUTORESET;
-    int32_t read_slot = wk.read_slot, write_slot = wk.write_slot, mode = wk.mode;
-    if (a.stochastic_delays) {
-      const uint32_t w = scg::philox_word(a.key0, a.key1, static_cast<uint32_t>(a.env_offset + n), episode,
-                                          static_cast<uint32_t>(wk.week - 1), SCG_STREAM_BG2_DELAY);
-      const int32_t d = a.delay_lo + static_cast<int32_t>((static_cast<uint64_t>(w) * static_cast<uint32_t>(a.delay_hi - a.delay_lo)) >> 32);
-      read_slot = wk.week % a.ring_slots;
-      write_slot = (wk.week + d) % a.ring_slots;
-      mode = d == 0 ? MODE_DIRECT : (wk.week + d > a.max_weeks ? MODE_DROP : MODE_ADD);
-    }
-    int32_t due[L], obs[L], ship[L], cur[L];
-    int32_t(&act)[L] = group_act[u];
-    zero_row<L>(due);
-    zero_row<L>(cur);
-    if (read_slot >= 0) ring.load(read_slot, due);
-    if (mode == MODE_ADD) ring.load(write_slot, cur);
-    if (autoreset) {  // the step kernel starts an auto-reset week's ledgers from zero (they end zeroed)
-      zero_row<L>(iacc);
-      zero_row<L>(bacc);
-      zero_row<L>(pacc);
-    }
-    const int32_t demand = a.demand_mode == SCG_DEMAND_FIXED ? wk.demand_fixed : week_demand(a, n, wk.week, episode);
-    const int32_t reward = week2_update<L>(a, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship, obs, iacc, bacc,
-                                           pacc, ovf);
-    if (a.stochastic_delays) {  // consumed: the slot is reused R weeks on
-      zero_row<L>(due);
-      ring.store(read_slot, due);
-    }
-    if (mode == MODE_STORE) {
-      ring.store(write_slot, ship);
-    } else if (mode == MODE_ADD) {
-      add_ship<L>(cur, ship, ovf);
-      ring.store(write_slot, cur);
-    }
-    if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
-    ret += reward;
-    if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
-    if (autoreset) {  // reset_env in registers and on the ring view
-      int32_t v[L];
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        inv[l] = a.init_inv[l];
-        bk[l] = 0;
-        op[l] = a.orders_value;
-        iacc[l] = bacc[l] = pacc[l] = 0;
-        obs[l] = inv[l] + a.max_stock;
-        v[l] = 0;
-      }
-      if (a.stochastic_delays)
-        for (int s = 0; s < a.ring_slots; ++s) ring.store(s, v);
-#pragma unroll
-      for (int l = 0; l < L; ++l) v[l] = a.ship_value;
-      for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, v);
-      if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
-      ret = 0;
-      ++episode;
-    }
-    if (obs_out) store_row<L>(obs_out + k * stride + row, obs);
-    if (rew_out) rew_out[k * a.n + n] = reward;
-  }
-  }
-  store_row<L>(a.inv + row, inv);
-  store_row<L>(a.bk + row, bk);
-  store_row<L>(a.op + row, op);
-  if (a.inv_acc) store_row<L>(a.inv_acc + row, iacc);
-  if (a.bk_acc) store_row<L>(a.bk_acc + row, bacc);
-  if (a.pen_acc) store_row<L>(a.pen_acc + row, pacc);
-  if (a.ep_ret) a.ep_ret[n] = ret;
-  note_overflow(a.err, ovf);
-}
+// ---- rollouts: K weeks per launch (scg_bg_rollout, scg_bg_rollout_policy) ----------------
+// Where a rollout's action rows come from and what goes out per week. kGroup weeks run
+// between two waits on memory.
+//
+// Read: the rows are the caller's. A group's rows are all requested before its first week, so
+// a launch waits on memory once per group instead of once per week.
+constexpr int kRolloutGroup = 8;
 
-template <int L>
-__global__ __launch_bounds__(kBlock) void bg2_rollout_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
-                                                             const int32_t* __restrict__ acts, int32_t* __restrict__ obs_out,
-                                                             int32_t* __restrict__ rew_out) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (n >= a.n) return;
-  rollout2_body<L>(a, n, K, weeks, acts, obs_out, rew_out, RingHbm<L>{a.ring, a.n * L, n * L});
-}
+struct RolloutActs {
+  static constexpr bool kPolicy = false;
+  static constexpr int kGroup = kRolloutGroup;
+  const int32_t* acts;  // [K][N][L] of this launch
+  int32_t* obs_out;     // [K][N][L] or null
+  int32_t* rew_out;     // [K][N] or null
+};
 
-template <int L>
-__global__ __launch_bounds__(kBlock) void bg2_rollout_lds_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
-                                                                 const int32_t* __restrict__ acts,
-                                                                 int32_t* __restrict__ obs_out,
-                                                                 int32_t* __restrict__ rew_out) {
-  extern __shared__ int32_t lds_ring[];
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (n >= a.n) return;  // lanes only touch their own LDS column: no block barrier needed
-  const RingHbm<L> hbm{a.ring, a.n * L, n * L};
-  const RingLds<L> lds{lds_ring + threadIdx.x};
-  for (int s = 0; s < a.ring_slots; ++s) {
-    int32_t v[L];
-    hbm.load(s, v);
-    lds.store(s, v);
-  }
-  rollout2_body<L>(a, n, K, weeks, acts, obs_out, rew_out, lds);
-  for (int s = 0; s < a.ring_slots; ++s) {
-    int32_t v[L];
-    lds.load(s, v);
-    hbm.store(s, v);
-  }
-}
-
-// ---- closed-loop rollouts with a per-env linear policy (scg_bg_rollout_policy) ------------
-// The rollout kernels above with the action row computed instead of read: each lane loads its
-// L*(L+1) parameter words once per launch (word q of a wave's 64 envs is one coalesced
-// 256-byte row) and keeps them in registers beside the state; each week it forms the
-// observation the env last produced from its inventory and backlog registers, the L int64
-// dot products, the shift and the clamp (scg_bg_policy.h), and then runs the week as the
-// open-loop bodies do. No action rows are requested, so the weeks are not grouped. Every
-// output is optional: with none, and the ring in LDS, a FIXED, POISSON or UNIFORM week touches
-// no HBM (history rows excepted). The sum of the launch's rewards is one int64 per lane.
-// The bodies are copies of rollout_body / rollout2_body on purpose: those keep their
-// generated code (DESIGN §6.1 on what a shared body cost the slab kernel's schedule).
+// Policy: the closed loop. Each lane loads its L*(L+1) parameter words once per launch (word q
+// of a wave's 64 envs is one coalesced 256-byte row) and keeps them in registers beside the
+// state; each week it forms the observation the env last produced from its inventory and
+// backlog registers, the L int64 dot products, the shift and the clamp (scg_bg_policy.h). No
+// action rows are requested, so the weeks are not grouped. Every output is optional: with
+// none, and the ring in LDS, a FIXED, POISSON or UNIFORM week touches no HBM (history rows
+// excepted). The sum of the launch's rewards is one int64 per lane.
 struct PolicyArgs {
+  static constexpr bool kPolicy = true;
+  static constexpr int kGroup = 1;
   const int32_t* params;  // [L*(L+1)][N]
   int32_t* acts_out;      // [K][N][L] of this launch, or null
   int32_t* obs_out;       // [K][N][L] or null
@@ -1269,90 +1022,33 @@ struct PolicyArgs {
   int32_t first;          // the first launch of a call stores reward_sum, later ones add to it
 };
 
-template <int L, class Ring>
-__device__ __forceinline__ void policy_rollout_body(const BgArgs& a, int64_t n, int32_t K, const RolloutWeeks& weeks,
-                                                    const PolicyArgs& pa, const Ring& ring) {
-  const int64_t row = n * L;
-  const int64_t stride = a.n * L;
-  int32_t par[L * (L + 1)];
-  policy_load<L>(pa.params, a.n, n, par);
-  int32_t inv[L], bk[L], op[L], iacc[L], bacc[L];
-  load_row<L>(a.inv + row, inv);
-  load_row<L>(a.bk + row, bk);
-  load_row<L>(a.op + row, op);
-  zero_row<L>(iacc);
-  zero_row<L>(bacc);
-  if (a.inv_acc) load_row<L>(a.inv_acc + row, iacc);
-  if (a.bk_acc) load_row<L>(a.bk_acc + row, bacc);
-  int64_t ret = a.ep_ret ? a.ep_ret[n] : 0;
-  int64_t sum = 0;
-  uint32_t episode = a.episode;
-  bool ovf = false;
-  for (int32_t k = 0; k < K; ++k) {
-    const WeekInfo wk = weeks.wk[k];
-    int32_t o[L], act[L], due[L], obs[L], ship[L], cur[L];
-    policy_obs<L>(inv, bk, 0, o);
-    policy_act<L>(par, o, pa.clamp, act);
-    zero_row<L>(due);
-    if (wk.read_slot >= 0) ring.load(wk.read_slot, due);
-    int32_t demand;
-    if (a.demand_mode == SCG_DEMAND_FIXED)
-      demand = wk.demand_fixed;
-    else
-      demand = week_demand(a, n, wk.week, episode);
-    zero_row<L>(cur);
-    if (wk.mode == MODE_ADD) ring.load(wk.write_slot, cur);
-    const int32_t reward = week_update<L>(a.h, a.b, a.guard, demand, wk.mode == MODE_DIRECT, due, inv, bk, op, act, ship,
-                                          obs, cur, iacc, bacc, ovf);
-    if (wk.mode == MODE_STORE) {
-      ring.store(wk.write_slot, ship);
-    } else if (wk.mode == MODE_ADD) {
-      ring.store(wk.write_slot, cur);
-    }
-    if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
-    ret += reward;
-    sum += reward;
-    if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
-    if (wk.flags & WEEK_AUTORESET) {  // auto-reset in registers (:140-156)
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        inv[l] = a.init_inv[l];
-        bk[l] = 0;
-        op[l] = a.orders_value;
-        iacc[l] = bacc[l] = 0;
-        obs[l] = inv[l];
-      }
-      int32_t init[L];
-#pragma unroll
-      for (int l = 0; l < L; ++l) init[l] = a.ship_value;
-      for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, init);
-      if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
-      ret = 0;
-      ++episode;
-    }
-    if (pa.acts_out) store_row<L>(pa.acts_out + k * stride + row, act);
-    if (pa.obs_out) store_row<L>(pa.obs_out + k * stride + row, obs);
-    if (pa.rew_out) pa.rew_out[k * a.n + n] = reward;
-  }
-  store_row<L>(a.inv + row, inv);
-  store_row<L>(a.bk + row, bk);
-  store_row<L>(a.op + row, op);
-  if (a.inv_acc) store_row<L>(a.inv_acc + row, iacc);
-  if (a.bk_acc) store_row<L>(a.bk_acc + row, bacc);
-  if (a.ep_ret) a.ep_ret[n] = ret;
-  if (pa.reward_sum) pa.reward_sum[n] = pa.first ? sum : pa.reward_sum[n] + sum;
-  note_overflow(a.err, ovf);
+// A rollout week's customer demand.
+__device__ __forceinline__ int32_t rollout_demand(const BgArgs& a, const WeekInfo& wk, int64_t n, uint32_t episode) {
+  return a.demand_mode == SCG_DEMAND_FIXED ? wk.demand_fixed : week_demand(a, n, wk.week, episode);
 }
 
-// BeerGameEnv2: rollout2_body's week (per-lane stochastic-delay slots, the in-register reset)
-// behind the same policy; the observation carries max_stock.
-template <int L, class Ring>
-__device__ __forceinline__ void policy_rollout2_body(const BgArgs& a, int64_t n, int32_t K, const RolloutWeeks& weeks,
-                                                     const PolicyArgs& pa, const Ring& ring) {
+// K weeks of one env: inventory, backlog, orders, the ledgers and the return stay in
+// registers; per week only the action row in (Read) and the obs / reward (and history) rows
+// out touch HBM, 36 B per env-week at L = 4, and everything else is written once at the end.
+// The ring view is RingLds, staged in shared memory for the whole launch, or RingHbm, whose
+// rows are read-modify-written through L2.
+// Variant 1 is BeerGameEnv (week_update, which also accumulates the slot it ships into);
+// variant 2 is BeerGameEnv2 (week2_update, a third ledger, max_stock in the observation).
+// With a delay list the host's weeks give the ring slots and modes; with variant 2's
+// stochastic delays each lane draws its own week's delay under the in-register episode, clears
+// the slot it received and read-modify-writes the slot it ships into, so slots differ between
+// lanes: both ring views take a per-lane slot (in LDS a lane only ever touches its own column,
+// whatever the slot). An auto-reset inside the launch is reset_env on the ring view and the
+// registers.
+template <int L, int Variant, class Source, class Ring>
+__device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t K, const RolloutWeeks& weeks,
+                                             const Source& src, const Ring& ring) {
+  constexpr bool kV2 = Variant == 2;
+  constexpr int G = Source::kGroup;
   const int64_t row = n * L;
   const int64_t stride = a.n * L;
-  int32_t par[L * (L + 1)];
-  policy_load<L>(pa.params, a.n, n, par);
+  [[maybe_unused]] int32_t par[L * (L + 1)];
+  if constexpr (Source::kPolicy) policy_load<L>(src.params, a.n, n, par);
   int32_t inv[L], bk[L], op[L], iacc[L], bacc[L], pacc[L];
   load_row<L>(a.inv + row, inv);
   load_row<L>(a.bk + row, bk);
@@ -1362,90 +1058,128 @@ __device__ __forceinline__ void policy_rollout2_body(const BgArgs& a, int64_t n,
   zero_row<L>(pacc);
   if (a.inv_acc) load_row<L>(a.inv_acc + row, iacc);
   if (a.bk_acc) load_row<L>(a.bk_acc + row, bacc);
-  if (a.pen_acc) load_row<L>(a.pen_acc + row, pacc);
+  if constexpr (kV2)
+    if (a.pen_acc) load_row<L>(a.pen_acc + row, pacc);
   int64_t ret = a.ep_ret ? a.ep_ret[n] : 0;
   int64_t sum = 0;
   uint32_t episode = a.episode;
   bool ovf = false;
-  for (int32_t k = 0; k < K; ++k) {
-    const WeekInfo wk = weeks.wk[k];
-    const bool autoreset = wk.flags & WEEK_AUTORESET;
-    int32_t read_slot = wk.read_slot, write_slot = wk.write_slot, mode = wk.mode;
-    if (a.stochastic_delays) {
-      const uint32_t w = scg::philox_word(a.key0, a.key1, static_cast<uint32_t>(a.env_offset + n), episode,
-                                          static_cast<uint32_t>(wk.week - 1), SCG_STREAM_BG2_DELAY);
-      const int32_t d = a.delay_lo + static_cast<int32_t>((static_cast<uint64_t>(w) * static_cast<uint32_t>(a.delay_hi - a.delay_lo)) >> 32);
-      read_slot = wk.week % a.ring_slots;
-      write_slot = (wk.week + d) % a.ring_slots;
-      mode = d == 0 ? MODE_DIRECT : (wk.week + d > a.max_weeks ? MODE_DROP : MODE_ADD);
-    }
-    int32_t o[L], act[L], due[L], obs[L], ship[L], cur[L];
-    policy_obs<L>(inv, bk, a.max_stock, o);
-    policy_act<L>(par, o, pa.clamp, act);
-    zero_row<L>(due);
-    zero_row<L>(cur);
-    if (read_slot >= 0) ring.load(read_slot, due);
-    if (mode == MODE_ADD) ring.load(write_slot, cur);
-    if (autoreset) {  // the step kernel starts an auto-reset week's ledgers from zero (they end zeroed)
-      zero_row<L>(iacc);
-      zero_row<L>(bacc);
-      zero_row<L>(pacc);
-    }
-    const int32_t demand = a.demand_mode == SCG_DEMAND_FIXED ? wk.demand_fixed : week_demand(a, n, wk.week, episode);
-    const int32_t reward = week2_update<L>(a, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship, obs, iacc, bacc,
-                                           pacc, ovf);
-    if (a.stochastic_delays) {  // consumed: the slot is reused R weeks on
-      zero_row<L>(due);
-      ring.store(read_slot, due);
-    }
-    if (mode == MODE_STORE) {
-      ring.store(write_slot, ship);
-    } else if (mode == MODE_ADD) {
-      add_ship<L>(cur, ship, ovf);
-      ring.store(write_slot, cur);
-    }
-    if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
-    ret += reward;
-    sum += reward;
-    if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
-    if (autoreset) {  // reset_env in registers and on the ring view
-      int32_t v[L];
+  for (int32_t k0 = 0; k0 < K; k0 += G) {
+    int32_t group_act[G][L];
+    if constexpr (!Source::kPolicy) {
 #pragma unroll
-      for (int l = 0; l < L; ++l) {
-        inv[l] = a.init_inv[l];
-        bk[l] = 0;
-        op[l] = a.orders_value;
-        iacc[l] = bacc[l] = pacc[l] = 0;
-        obs[l] = inv[l] + a.max_stock;
-        v[l] = 0;
+      for (int u = 0; u < G; ++u)
+        if (k0 + u < K) load_row<L>(src.acts + (k0 + u) * stride + row, group_act[u]);
+    }
+    // the group's weeks, for (u = 0; u < G; ++u) with a tail check, written rotated: a group of
+    // one is then no loop at all (as an inner loop of one trip it cost the closed loop 2 %)
+    int u = 0;
+#pragma unroll
+    do {
+      const int32_t k = k0 + u;
+      if (G > 1 && k >= K) break;
+      const WeekInfo wk = weeks.wk[k];
+      const bool autoreset = wk.flags & WEEK_AUTORESET;
+      int32_t read_slot = wk.read_slot, write_slot = wk.write_slot, mode = wk.mode;
+      if constexpr (kV2) {
+        if (a.stochastic_delays) {
+          const uint32_t w = scg::philox_word(a.key0, a.key1, static_cast<uint32_t>(a.env_offset + n), episode,
+                                              static_cast<uint32_t>(wk.week - 1), SCG_STREAM_BG2_DELAY);
+          const int32_t d = a.delay_lo + static_cast<int32_t>((static_cast<uint64_t>(w) * static_cast<uint32_t>(a.delay_hi - a.delay_lo)) >> 32);
+          read_slot = wk.week % a.ring_slots;
+          write_slot = (wk.week + d) % a.ring_slots;
+          mode = d == 0 ? MODE_DIRECT : (wk.week + d > a.max_weeks ? MODE_DROP : MODE_ADD);
+        }
       }
-      if (a.stochastic_delays)
-        for (int s = 0; s < a.ring_slots; ++s) ring.store(s, v);
+      int32_t due[L], obs[L], ship[L], cur[L];
+      int32_t(&act)[L] = group_act[u];
+      if constexpr (Source::kPolicy) {
+        int32_t o[L];
+        policy_obs<L>(inv, bk, kV2 ? a.max_stock : 0, o);
+        policy_act<L>(par, o, src.clamp, act);
+      }
+      // the demand draw stands where each variant's kernels have had it, before or after the
+      // request for the row the week ships into: moved, it changes their registers and schedule
+      int32_t demand;
+      zero_row<L>(due);
+      if (read_slot >= 0) ring.load(read_slot, due);
+      if constexpr (!kV2) demand = rollout_demand(a, wk, n, episode);
+      zero_row<L>(cur);
+      if (mode == MODE_ADD) ring.load(write_slot, cur);
+      if constexpr (kV2) {
+        if (autoreset) {  // the step kernel starts an auto-reset week's ledgers from zero (they end zeroed)
+          zero_row<L>(iacc);
+          zero_row<L>(bacc);
+          zero_row<L>(pacc);
+        }
+        demand = rollout_demand(a, wk, n, episode);
+      }
+      int32_t reward;
+      if constexpr (kV2)
+        reward = week2_update<L>(a, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship, obs, iacc, bacc, pacc, ovf);
+      else
+        reward = week_update<L>(a.h, a.b, a.guard, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship, obs, cur, iacc,
+                                bacc, ovf);
+      if constexpr (kV2) {
+        if (a.stochastic_delays) {  // consumed: the slot is reused R weeks on
+          zero_row<L>(due);
+          ring.store(read_slot, due);
+        }
+      }
+      if (mode == MODE_STORE) {
+        ring.store(write_slot, ship);
+      } else if (mode == MODE_ADD) {
+        if constexpr (kV2) add_ship<L>(cur, ship, ovf);
+        ring.store(write_slot, cur);
+      }
+      if (a.hist) store_row<L>(a.hist + static_cast<int64_t>(wk.week) * stride + row, op);
+      ret += reward;
+      sum += reward;
+      if ((wk.flags & WEEK_TERMINAL) && a.final_ret) a.final_ret[n] = ret;
+      if (autoreset) {  // reset_env in registers and on the ring view (:140-156)
+        int32_t v[L];
 #pragma unroll
-      for (int l = 0; l < L; ++l) v[l] = a.ship_value;
-      for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, v);
-      if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
-      ret = 0;
-      ++episode;
-    }
-    if (pa.acts_out) store_row<L>(pa.acts_out + k * stride + row, act);
-    if (pa.obs_out) store_row<L>(pa.obs_out + k * stride + row, obs);
-    if (pa.rew_out) pa.rew_out[k * a.n + n] = reward;
+        for (int l = 0; l < L; ++l) {
+          inv[l] = a.init_inv[l];
+          bk[l] = 0;
+          op[l] = a.orders_value;
+          iacc[l] = bacc[l] = pacc[l] = 0;
+          obs[l] = inv[l] + (kV2 ? a.max_stock : 0);
+          v[l] = 0;
+        }
+        if constexpr (kV2) {
+          if (a.stochastic_delays)
+            for (int s = 0; s < a.ring_slots; ++s) ring.store(s, v);
+        }
+#pragma unroll
+        for (int l = 0; l < L; ++l) v[l] = a.ship_value;
+        for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, v);
+        if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
+        ret = 0;
+        ++episode;
+      }
+      if constexpr (Source::kPolicy)
+        if (src.acts_out) store_row<L>(src.acts_out + k * stride + row, act);
+      if (src.obs_out) store_row<L>(src.obs_out + k * stride + row, obs);
+      if (src.rew_out) src.rew_out[k * a.n + n] = reward;
+    } while (G > 1 && ++u < G);
   }
   store_row<L>(a.inv + row, inv);
   store_row<L>(a.bk + row, bk);
   store_row<L>(a.op + row, op);
   if (a.inv_acc) store_row<L>(a.inv_acc + row, iacc);
   if (a.bk_acc) store_row<L>(a.bk_acc + row, bacc);
-  if (a.pen_acc) store_row<L>(a.pen_acc + row, pacc);
+  if constexpr (kV2)
+    if (a.pen_acc) store_row<L>(a.pen_acc + row, pacc);
   if (a.ep_ret) a.ep_ret[n] = ret;
-  if (pa.reward_sum) pa.reward_sum[n] = pa.first ? sum : pa.reward_sum[n] + sum;
+  if constexpr (Source::kPolicy)
+    if (src.reward_sum) src.reward_sum[n] = src.first ? sum : src.reward_sum[n] + sum;
   note_overflow(a.err, ovf);
 }
 
 // The ring of one lane between HBM and its LDS column, around a launch.
 template <int L>
-__device__ __forceinline__ void policy_ring_copy(const RingHbm<L>& hbm, const RingLds<L>& lds, int32_t slots, bool in) {
+__device__ __forceinline__ void ring_copy(const RingHbm<L>& hbm, const RingLds<L>& lds, int32_t slots, bool in) {
   for (int s = 0; s < slots; ++s) {
     int32_t v[L];
     if (in) {
@@ -1458,50 +1192,25 @@ __device__ __forceinline__ void policy_ring_copy(const RingHbm<L>& hbm, const Ri
   }
 }
 
-template <int L>
-__global__ __launch_bounds__(kBlock) void bg_policy_rollout_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
-                                                                   const PolicyArgs pa) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (n >= a.n) return;
-  policy_rollout_body<L>(a, n, K, weeks, pa, RingHbm<L>{a.ring, a.n * L, n * L});
-}
-
-template <int L>
-__global__ __launch_bounds__(kBlock) void bg_policy_rollout_lds_kernel(const BgArgs a, int32_t K,
-                                                                       const RolloutWeeks weeks, const PolicyArgs pa) {
-  extern __shared__ int32_t lds_ring[];
+template <int L, int Variant, class Source, bool kLds>
+__global__ __launch_bounds__(kBlock) void bg_rollout_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
+                                                            const Source src) {
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (n >= a.n) return;  // lanes only touch their own LDS column: no block barrier needed
   const RingHbm<L> hbm{a.ring, a.n * L, n * L};
-  const RingLds<L> lds{lds_ring + threadIdx.x};
-  policy_ring_copy<L>(hbm, lds, a.ring_slots, true);
-  policy_rollout_body<L>(a, n, K, weeks, pa, lds);
-  policy_ring_copy<L>(hbm, lds, a.ring_slots, false);
+  if constexpr (kLds) {
+    extern __shared__ int32_t lds_ring[];
+    const RingLds<L> lds{lds_ring + threadIdx.x};
+    ring_copy<L>(hbm, lds, a.ring_slots, true);
+    rollout_body<L, Variant>(a, n, K, weeks, src, lds);
+    ring_copy<L>(hbm, lds, a.ring_slots, false);
+  } else {
+    rollout_body<L, Variant>(a, n, K, weeks, src, hbm);
+  }
 }
 
-template <int L>
-__global__ __launch_bounds__(kBlock) void bg2_policy_rollout_kernel(const BgArgs a, int32_t K, const RolloutWeeks weeks,
-                                                                    const PolicyArgs pa) {
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (n >= a.n) return;
-  policy_rollout2_body<L>(a, n, K, weeks, pa, RingHbm<L>{a.ring, a.n * L, n * L});
-}
-
-template <int L>
-__global__ __launch_bounds__(kBlock) void bg2_policy_rollout_lds_kernel(const BgArgs a, int32_t K,
-                                                                        const RolloutWeeks weeks, const PolicyArgs pa) {
-  extern __shared__ int32_t lds_ring[];
-  const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (n >= a.n) return;  // lanes only touch their own LDS column: no block barrier needed
-  const RingHbm<L> hbm{a.ring, a.n * L, n * L};
-  const RingLds<L> lds{lds_ring + threadIdx.x};
-  policy_ring_copy<L>(hbm, lds, a.ring_slots, true);
-  policy_rollout2_body<L>(a, n, K, weeks, pa, lds);
-  policy_ring_copy<L>(hbm, lds, a.ring_slots, false);
-}
-
-// The policy rollout of `variant` at L levels (1..SCG_BG_POLICY_MAX_LEVELS), by the ring rule
-// of bg_launch_rollout; defined in scg_bg_policy.hip, the unit that instantiates these kernels.
+// The policy rollout at L levels (1..SCG_BG_POLICY_MAX_LEVELS); defined in scg_bg_policy.hip, the
+// unit that instantiates the closed-loop kernels.
 int bg_launch_policy_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
                              const RolloutWeeks& weeks, const PolicyArgs& pa);
 
@@ -1586,47 +1295,35 @@ int bg_launch_slab(int demand_mode, dim3 grid, hipStream_t s, const SlabLaunch& 
   });
 }
 
-template <int L>
-int bg_launch_rollout(dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, const RolloutWeeks& weeks,
-                      const int32_t* acts, int32_t* obs, int32_t* rew) {
+// Either source's rollout of `variant`: the ring is staged in LDS for the launch when the
+// block's share of it fits 64 KiB, else left in HBM.
+template <int L, class Source>
+int bg_launch_rollout(int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, const RolloutWeeks& weeks,
+                      const Source& src) {
   const size_t lds = static_cast<size_t>(a.ring_slots) * L * kBlock * sizeof(int32_t);
-  if (lds <= 64 * 1024) {  // ring staged in LDS for the launch
-    hipLaunchKernelGGL(bg_rollout_lds_kernel<L>, grid, dim3(kBlock), lds, s, a, K, weeks, acts, obs, rew);
-    return check_launch("bg_rollout_lds_kernel");
-  }
-  hipLaunchKernelGGL(bg_rollout_kernel<L>, grid, dim3(kBlock), 0, s, a, K, weeks, acts, obs, rew);
-  return check_launch("bg_rollout_kernel");
+  const auto launch = [&](auto v, auto in_lds) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(bg_rollout_kernel<L, decltype(v)::value, Source, decltype(in_lds)::value>), grid,
+                       dim3(kBlock), in_lds ? lds : 0, s, a, K, weeks, src);
+    return check_launch(in_lds ? "bg_rollout_kernel (ring in LDS)" : "bg_rollout_kernel (ring in HBM)");
+  };
+  const auto ring = [&](auto v) { return lds <= 64 * 1024 ? launch(v, std::true_type{}) : launch(v, std::false_type{}); };
+  return variant == 2 ? ring(std::integral_constant<int, 2>{}) : ring(std::integral_constant<int, 1>{});
 }
 
-// BeerGameEnv2's pair, by the same ring rule.
-template <int L>
-int bg_launch_rollout2(dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, const RolloutWeeks& weeks,
-                       const int32_t* acts, int32_t* obs, int32_t* rew) {
-  const size_t lds = static_cast<size_t>(a.ring_slots) * L * kBlock * sizeof(int32_t);
-  if (lds <= 64 * 1024) {
-    hipLaunchKernelGGL(bg2_rollout_lds_kernel<L>, grid, dim3(kBlock), lds, s, a, K, weeks, acts, obs, rew);
-    return check_launch("bg2_rollout_lds_kernel");
-  }
-  hipLaunchKernelGGL(bg2_rollout_kernel<L>, grid, dim3(kBlock), 0, s, a, K, weeks, acts, obs, rew);
-  return check_launch("bg2_rollout_kernel");
-}
-
-// One level's seven launchers; scg_beergame.hip keeps a table of them by L.
+// One level's six launchers; scg_beergame.hip keeps a table of them by L.
 struct BgLaunchers {
   int (*reset)(dim3, hipStream_t, const BgArgs&);
   int (*step2)(dim3, hipStream_t, const BgArgs&, const WeekInfo&);
   int (*step)(dim3, hipStream_t, const BgArgs&, const WeekInfo&, hipEvent_t, hipEvent_t);
   int (*server)(hipStream_t, int, scg_bg_server_box*, uint32_t, uint32_t);
   int (*slab)(int, dim3, hipStream_t, const SlabLaunch&, hipEvent_t, hipEvent_t);
-  int (*rollout)(dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&, const int32_t*, int32_t*, int32_t*);
-  int (*rollout2)(dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&, const int32_t*, int32_t*, int32_t*);
+  int (*rollout)(int variant, dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&, const RolloutActs&);
 };
 
 template <int L>
 const BgLaunchers* bg_launchers() {
   static const BgLaunchers k{bg_launch_reset<L>, bg_launch_step2<L>, bg_launch_step<L>,
-                             bg_launch_server<L>, bg_launch_slab<L>, bg_launch_rollout<L>,
-                             bg_launch_rollout2<L>};
+                             bg_launch_server<L>, bg_launch_slab<L>, bg_launch_rollout<L, RolloutActs>};
   return &k;
 }
 

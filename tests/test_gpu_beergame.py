@@ -228,11 +228,11 @@ def test_autoreset_across_episodes_matches_oracle():
         assert env.week == 0 and env.episode == ep + 1
 
 
-def test_rollout_equals_steps_across_episode_end():
+def _assert_rollout_equals_steps(N, info, seed=5):
+    """A twin pair from reset over three 12-week episodes and five weeks: one env steps, the other
+    rolls out in one call; every obs and reward and the state afterwards are equal."""
     from gym_supplychain_amd import BeerGameVecEnv
-    N, T, L, seed = 3000, 12, 5, 5
-    info = dict(levels=L, initial_inventory=[12, 8, 4, 9, 1], customer_demand=[0] * T,
-                shipment_delays=[2, 0, 3, 1, 1, 4, 2, 0, 5, 1, 2, 3])
+    T, L = len(info["customer_demand"]), info["levels"]
     K = 3 * T + 5
     acts = _uniform_actions_dev(seed, N, K, L, 7, -3, 7)
     a = BeerGameVecEnv(N, info, demand="poisson", poisson_lambda=6.0, seed=seed, device=DEV)
@@ -247,6 +247,28 @@ def test_rollout_equals_steps_across_episode_end():
               "final_return"):
         assert torch.equal(getattr(a, t), getattr(b, t)), t
     assert (a.week, a.episode) == (b.week, b.episode)
+    return a, b
+
+
+def test_rollout_equals_steps_across_episode_end():
+    T = 12
+    _assert_rollout_equals_steps(3000, dict(levels=5, initial_inventory=[12, 8, 4, 9, 1], customer_demand=[0] * T,
+                                            shipment_delays=[2, 0, 3, 1, 1, 4, 2, 0, 5, 1, 2, 3]))
+
+
+@pytest.mark.parametrize("max_delay", [3, 5], ids=["lds", "hbm"])
+def test_rollout_equals_steps_at_16_levels(max_delay):
+    """L = 16, the most a rollout takes: 4 ring slots x 16 levels x 256 lanes is the LDS ring at
+    exactly 64 KiB, 6 slots the HBM ring. 300 envs: a full block and a 44-lane tail; 41 weeks:
+    auto-resets inside the launch and a last group of one week."""
+    T, L = 12, 16
+    delays = [2, 0, 3, 1, 1, max_delay, 2, 0, max_delay, 1, 2, 3]
+    stepped, env = _assert_rollout_equals_steps(300, dict(levels=L, initial_inventory=list(range(3, 3 + L)),
+                                                          customer_demand=[0] * T, shipment_delays=delays))
+    assert torch.equal(stepped._ring, env._ring)
+    assert env.ring_slots == max_delay + 1 and (env.week, env.episode) == (5, 3)
+    stepped.check_errors()
+    env.check_errors()
 
 
 def test_sharding_is_invariant():

@@ -1,7 +1,7 @@
-"""BeerGame2VecEnv.rollout (scg_bg_rollout on a variant-2 config: bg2_rollout_kernel /
-bg2_rollout_lds_kernel): K weeks in one call against the reference's golden episodes, against a
-twin env stepped week by week, and against the oracle. Every comparison is exact. N = 300 is
-one full 256-lane block and a 44-lane tail."""
+"""BeerGame2VecEnv.rollout (scg_bg_rollout on a variant-2 config: bg_rollout_kernel's variant 2
+reading action rows, ring in LDS or in HBM): K weeks in one call against the reference's golden
+episodes, against a twin env stepped week by week, and against the oracle. Every comparison is
+exact. N = 300 is one full 256-lane block and a 44-lane tail."""
 import ctypes
 
 import numpy as np

@@ -1,6 +1,7 @@
-"""BeerGameVecEnv.rollout_policy / BeerGame2VecEnv.rollout_policy (scg_bg_rollout_policy: the
-bg_policy_rollout and bg2_policy_rollout kernels and their LDS twins): closed-loop weeks in one
-call against a twin env stepped week by week with the NumPy restatement of the policy
+"""BeerGameVecEnv.rollout_policy / BeerGame2VecEnv.rollout_policy (scg_bg_rollout_policy:
+bg_rollout_kernel with the policy as its source, both variants, ring in LDS or in HBM):
+closed-loop weeks in one call against a twin env stepped week by week with the NumPy restatement
+of the policy
 (tests/bg_policy_ref.py) applied to its own last observation, and against the oracle. Every
 comparison is exact. N = 300 is one full 256-lane block and a 44-lane tail.
 
@@ -129,9 +130,14 @@ def test_policy_equals_twin_variant1():
     env.check_errors()
 
 
-@pytest.mark.parametrize("L", [1, 3, 8])
-def test_policy_equals_twin_variant1_levels(L):
-    _assert_policy_equals_twin(lambda: _env1(L=L), L, 3 * T + 5, clip=CLIP1)
+@pytest.mark.parametrize("L,weeks,K", [(1, T, 3 * T + 5), (3, T, 3 * T + 5), (8, T, 3 * T + 5), (4, 50, 135)],
+                         ids=["1", "3", "8", "launch-cut"])
+def test_policy_equals_twin_variant1_levels(L, weeks, K):
+    """launch-cut: 135 weeks of 50-week episodes in one call, launches of 128 + 7 weeks with two
+    auto-resets inside the first and the cut mid-episode."""
+    delays = (LIST_DELAYS * 5)[:weeks]
+    env, _ = _assert_policy_equals_twin(lambda: _env1(L=L, delays=delays, weeks=weeks), L, K, clip=CLIP1)
+    assert (env.week, env.episode) == (K % weeks, K // weeks)
 
 
 # ---- 2. twin, variant 2: default clip, penalty ledger, launch boundaries, auto-resets ----------

@@ -6,7 +6,7 @@ BeerGame2VecEnv at L = 4, 35 weeks, customer_demand=(0, 16), shipment_delays=(0,
 demand and per-env random delays, ledgers and returns kept, auto-reset). A sample is the wall
 clock of `--episodes` whole episodes between two device synchronisations: as 35 step() calls
 per episode (bg2_step_kernel, one launch per week) or as one rollout() of 35 weeks per episode
-(bg2_rollout_lds_kernel). The two alternate, `--pairs` times, after one untimed sample of each;
+(bg_rollout_kernel, variant 2, ring in LDS). The two alternate, `--pairs` times, after one untimed sample of each;
 before that one episode of both is compared bit for bit. Prints one JSON line per sample and a
 summary line: medians and max - min of the time per env-step, and whether the rollout's median
 lies below the step loop's by more than the step loop's own max - min (DESIGN §6.1's rule).
