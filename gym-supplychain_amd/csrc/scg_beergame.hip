@@ -685,6 +685,79 @@ int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_
   });
 }
 
+// ---- the local-information policy (scg_bg_local.h) ---------------------------------------
+// What the in-transit sum needs of a config: every delay within the 64-bit live mask, and the
+// ring (a full table keeps rows past T, which would need a different rule).
+static int check_local_config(const scg_bg_config* cfg) {
+  if (cfg->levels > SCG_BG_POLICY_MAX_LEVELS)
+    return fail(SCG_ERR_INVALID, "local policy: levels=%d above %d", cfg->levels, SCG_BG_POLICY_MAX_LEVELS);
+  if (cfg->full_table) return fail(SCG_ERR_INVALID, "local policy: full_table configs are not supported");
+  for (int32_t w = 0; w <= cfg->max_weeks; ++w)
+    if (cfg->shipment_delays[w] > kLocalMaxDelay)
+      return fail(SCG_ERR_INVALID, "local policy: shipment_delays[%d]=%d above SCG_BG_LOCAL_MAX_DELAY=%d", w,
+                  cfg->shipment_delays[w], kLocalMaxDelay);
+  if (cfg->stochastic_delays && cfg->delay_hi - 1 > kLocalMaxDelay)
+    return fail(SCG_ERR_INVALID, "local policy: stochastic delays up to delay_hi-1=%d above SCG_BG_LOCAL_MAX_DELAY=%d",
+                cfg->delay_hi - 1, kLocalMaxDelay);
+  return SCG_OK;
+}
+
+// The live mask of the state after week w0, and the FIXED demand of that week.
+static uint64_t local_mask(const scg_bg_config* cfg, int32_t w0) {
+  return cfg->stochastic_delays ? local_live_mask_stochastic(cfg->ring_slots, cfg->max_weeks, w0)
+                                : local_live_mask(cfg->shipment_delays, cfg->max_weeks, w0);
+}
+static int32_t local_last_fixed(const scg_bg_config* cfg, int32_t w0) {
+  return (cfg->demand_mode == SCG_DEMAND_FIXED && w0 >= 1) ? cfg->customer_demand[w0 - 1] : 0;
+}
+
+int scg_bg_rollout_local(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_local_policy* policy,
+                         int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum, uint32_t flags,
+                         void* stream) {
+  if (int rc = check_state(cfg, st)) return rc;
+  if (!policy || !policy->params) return fail(SCG_ERR_INVALID, "local policy rollout needs a policy with params");
+  if (policy->kind != SCG_BG_POLICY_LOCAL) return fail(SCG_ERR_INVALID, "unknown local policy kind %d", policy->kind);
+  if (!local_valid(policy->kind, policy->shift, policy->act_lo, policy->act_hi))
+    return fail(SCG_ERR_INVALID, "local policy needs shift in 0..%d and act_lo <= act_hi (got shift=%d, clamp %d..%d)",
+                kPolicyMaxShift, policy->shift, policy->act_lo, policy->act_hi);
+  if (int rc = check_local_config(cfg)) return rc;
+  if (n_weeks < 0) return fail(SCG_ERR_INVALID, "local policy rollout needs n_weeks >= 0");
+  if (int rc = check_step(cfg, st)) return rc;
+  if (int rc = check_horizon(cfg, st, n_weeks, flags)) return rc;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_weeks == 0) {  // no launch: the sum of no rewards
+    if (reward_sum && hipMemsetAsync(reward_sum, 0, static_cast<size_t>(st->n_envs) * sizeof(int64_t), s) != hipSuccess)
+      return fail(SCG_ERR_HIP, "hipMemsetAsync(reward_sum) failed");
+    return SCG_OK;
+  }
+  const int64_t stride = st->n_envs * cfg->levels;
+  return rollout_launches(cfg, st, n_weeks, flags, [&](int32_t done_k, int32_t K, const BgArgs& a, const RolloutWeeks& weeks) {
+    const int32_t w0 = st->week;  // the state this launch starts from (weeks.wk[0].week - 1)
+    LocalArgs la;
+    la.params = policy->params;
+    la.acts_out = actions_out ? actions_out + done_k * stride : nullptr;
+    la.obs_out = obs ? obs + done_k * stride : nullptr;
+    la.rew_out = rewards ? rewards + done_k * st->n_envs : nullptr;
+    la.reward_sum = reward_sum;
+    la.clamp = PolicyClamp{policy->shift, policy->act_lo, policy->act_hi};
+    la.first = done_k == 0;
+    la.last_fixed = local_last_fixed(cfg, w0);
+    la.live = local_mask(cfg, w0);
+    return bg_launch_local_rollout(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, la);
+  });
+}
+
+int scg_bg_local_features(const scg_bg_config* cfg, const scg_bg_state* st, int32_t* out, void* stream) {
+  if (int rc = check_state(cfg, st)) return rc;
+  if (!out) return fail(SCG_ERR_INVALID, "local features: null output");
+  if (int rc = check_local_config(cfg)) return rc;
+  if (st->week < 0) return fail(SCG_ERR_NOT_RESET, "local features before reset()");
+  if (st->week > cfg->max_weeks) return fail(SCG_ERR_INVALID, "local features: week %d past the horizon %d", st->week, cfg->max_weeks);
+  const BgArgs a = make_args(cfg, st);
+  return bg_launch_local_features(grid_for(st->n_envs), static_cast<hipStream_t>(stream), a, cfg->levels, st->week,
+                                  local_mask(cfg, st->week), local_last_fixed(cfg, st->week), out);
+}
+
 int scg_bg_poisson_demand(const scg_bg_config* cfg, const scg_bg_state* st, uint32_t episode, int32_t* out,
                           void* stream) {
   if (int rc = check_state(cfg, st)) return rc;

@@ -3,7 +3,8 @@
 // rollout kernels, templated on the level count L, and one launcher per kernel family and
 // L. scg_beergame.hip dispatches on L at run time; the launchers are instantiated in four
 // units (levels 1-4, 5-8, 9-12, 13-16) that compile in parallel. The closed-loop policy
-// rollout kernels (levels 1-8) are instantiated, with their launcher, in scg_bg_policy.hip.
+// rollout kernels (levels 1-8) are instantiated, with their launcher, in scg_bg_policy.hip
+// (linear policy) and scg_bg_local.hip (local-information policy).
 //
 // BeerGame hot path for gfx950: reset / step / rollout kernels + their C-ABI launchers.
 //
@@ -31,6 +32,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "scg_bg_local.h"
 #include "scg_bg_plan.h"
 #include "scg_bg_policy.h"
 #include "scg_common.h"
@@ -997,6 +999,7 @@ constexpr int kRolloutGroup = 8;
 
 struct RolloutActs {
   static constexpr bool kPolicy = false;
+  static constexpr bool kLocal = false;
   static constexpr int kGroup = kRolloutGroup;
   const int32_t* acts;  // [K][N][L] of this launch
   int32_t* obs_out;     // [K][N][L] or null
@@ -1012,6 +1015,7 @@ struct RolloutActs {
 // excepted). The sum of the launch's rewards is one int64 per lane.
 struct PolicyArgs {
   static constexpr bool kPolicy = true;
+  static constexpr bool kLocal = false;
   static constexpr int kGroup = 1;
   const int32_t* params;  // [L*(L+1)][N]
   int32_t* acts_out;      // [K][N][L] of this launch, or null
@@ -1021,6 +1025,47 @@ struct PolicyArgs {
   PolicyClamp clamp;
   int32_t first;          // the first launch of a call stores reward_sum, later ones add to it
 };
+
+// Local: the closed loop with the local-information policy (scg_bg_local.h): 5*L parameter words
+// per lane, and beside the state two more things in registers, the in-transit sum of each level
+// and the last customer demand. Once per launch the lane adds the ring rows the host's mask
+// marks live (bit j-1: the row of week w0 + j, w0 the week the launch starts after) and takes
+// the demand of week w0 (FIXED: from the host; else the draw or table entry of that week; the
+// initial orders value at w0 = 0); each week updates both from registers.
+struct LocalArgs {
+  static constexpr bool kPolicy = true;
+  static constexpr bool kLocal = true;
+  static constexpr int kGroup = 1;
+  const int32_t* params;  // [5*L][N]
+  int32_t* acts_out;      // [K][N][L] of this launch, or null
+  int32_t* obs_out;       // [K][N][L] or null
+  int32_t* rew_out;       // [K][N] or null
+  int64_t* reward_sum;    // [N] or null
+  PolicyClamp clamp;
+  int32_t first;          // the first launch of a call stores reward_sum, later ones add to it
+  int32_t last_fixed;     // FIXED demand: customer_demand[w0 - 1] (unused at w0 = 0)
+  uint64_t live;          // local_live_mask of the launch's first state
+};
+
+// The sum of the ring rows `live` marks, from the state after week w0: transit[l] of
+// scg_bg_local.h, in wrapping arithmetic. `live` is uniform, so the loop is scalar.
+template <int L, class Ring>
+__device__ __forceinline__ void local_transit(const Ring& ring, uint64_t live, int32_t w0, int32_t slots,
+                                              int32_t (&transit)[L]) {
+  zero_row<L>(transit);
+  for (uint64_t m = live; m; m &= m - 1) {
+    int32_t v[L];
+    ring.load((w0 + 1 + __builtin_ctzll(m)) % slots, v);
+#pragma unroll
+    for (int l = 0; l < L; ++l) transit[l] = local_wrap_add(transit[l], v[l]);
+  }
+}
+
+// The customer demand of week w0, the week a launch starts after (last_fixed: the FIXED value).
+__device__ __forceinline__ int32_t local_last_demand(const BgArgs& a, int64_t n, int32_t w0, int32_t last_fixed) {
+  if (w0 == 0) return a.orders_value;
+  return a.demand_mode == SCG_DEMAND_FIXED ? last_fixed : week_demand(a, n, w0, a.episode);
+}
 
 // A rollout week's customer demand.
 __device__ __forceinline__ int32_t rollout_demand(const BgArgs& a, const WeekInfo& wk, int64_t n, uint32_t episode) {
@@ -1047,8 +1092,12 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
   constexpr int G = Source::kGroup;
   const int64_t row = n * L;
   const int64_t stride = a.n * L;
-  [[maybe_unused]] int32_t par[L * (L + 1)];
-  if constexpr (Source::kPolicy) policy_load<L>(src.params, a.n, n, par);
+  constexpr bool kLocal = Source::kLocal;
+  [[maybe_unused]] int32_t par[kLocal ? L * kLocalRow : L * (L + 1)];
+  if constexpr (kLocal)
+    local_load<L>(src.params, a.n, n, par);
+  else if constexpr (Source::kPolicy)
+    policy_load<L>(src.params, a.n, n, par);
   int32_t inv[L], bk[L], op[L], iacc[L], bacc[L], pacc[L];
   load_row<L>(a.inv + row, inv);
   load_row<L>(a.bk + row, bk);
@@ -1064,6 +1113,13 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
   int64_t sum = 0;
   uint32_t episode = a.episode;
   bool ovf = false;
+  [[maybe_unused]] int32_t transit[L];
+  [[maybe_unused]] int32_t last_demand = 0;
+  if constexpr (kLocal) {
+    const int32_t w0 = weeks.wk[0].week - 1;
+    local_transit<L>(ring, src.live, w0, a.ring_slots, transit);
+    last_demand = local_last_demand(a, n, w0, src.last_fixed);
+  }
   for (int32_t k0 = 0; k0 < K; k0 += G) {
     int32_t group_act[G][L];
     if constexpr (!Source::kPolicy) {
@@ -1096,7 +1152,13 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
       if constexpr (Source::kPolicy) {
         int32_t o[L];
         policy_obs<L>(inv, bk, kV2 ? a.max_stock : 0, o);
-        policy_act<L>(par, o, src.clamp, act);
+        if constexpr (kLocal) {
+          int32_t f[L][kLocalFeatures];
+          local_features<L>(o, bk, op, transit, last_demand, f);
+          local_act<L>(par, f, src.clamp, act);
+        } else {
+          policy_act<L>(par, o, src.clamp, act);
+        }
       }
       // the demand draw stands where each variant's kernels have had it, before or after the
       // request for the row the week ships into: moved, it changes their registers and schedule
@@ -1120,6 +1182,14 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
       else
         reward = week_update<L>(a.h, a.b, a.guard, demand, mode == MODE_DIRECT, due, inv, bk, op, act, ship, obs, cur, iacc,
                                 bacc, ovf);
+      if constexpr (kLocal) {  // what the week put into the pipeline, less what arrived
+        const bool lands = mode == MODE_STORE || mode == MODE_ADD;
+#pragma unroll
+        for (int l = 0; l < L; ++l)
+          transit[l] = static_cast<int32_t>(static_cast<uint32_t>(transit[l]) + static_cast<uint32_t>(lands ? ship[l] : 0) -
+                                            static_cast<uint32_t>(due[l]));
+        last_demand = demand;
+      }
       if constexpr (kV2) {
         if (a.stochastic_delays) {  // consumed: the slot is reused R weeks on
           zero_row<L>(due);
@@ -1155,6 +1225,12 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
         for (int l = 0; l < L; ++l) v[l] = a.ship_value;
         for (int t = 1; t <= a.init_slots; ++t) ring.store(t % a.ring_slots, v);
         if (a.hist) fill_row<L>(a.hist + row, a.orders_value);
+        if constexpr (kLocal) {
+#pragma unroll
+          for (int l = 0; l < L; ++l)
+            transit[l] = static_cast<int32_t>(static_cast<uint32_t>(a.init_slots) * static_cast<uint32_t>(a.ship_value));
+          last_demand = a.orders_value;
+        }
         ret = 0;
         ++episode;
       }
@@ -1213,6 +1289,14 @@ __global__ __launch_bounds__(kBlock) void bg_rollout_kernel(const BgArgs a, int3
 // unit that instantiates the closed-loop kernels.
 int bg_launch_policy_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
                              const RolloutWeeks& weeks, const PolicyArgs& pa);
+
+// The same for the local-information policy, and the features of the state as it stands
+// (out [N][L][4]; w0 = st->week, `live` its mask, last_fixed as in LocalArgs); both defined in
+// scg_bg_local.hip.
+int bg_launch_local_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
+                            const RolloutWeeks& weeks, const LocalArgs& la);
+int bg_launch_local_features(dim3 grid, hipStream_t s, const BgArgs& a, int32_t L, int32_t w0, uint64_t live,
+                             int32_t last_fixed, int32_t* out);
 
 // hipModuleLaunchKernel with the kernel's function handle resolved once per instantiation,
 // skipping the host-stub lookup of hipLaunchKernel on every step: ≈0.5 µs less host time

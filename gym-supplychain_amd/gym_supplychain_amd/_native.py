@@ -46,6 +46,9 @@ BG_ROLLOUT_MAX = 128
 BG_POLICY_LINEAR = 1  # scg_bg_policy.kind
 BG_POLICY_MAX_LEVELS = 8
 BG_POLICY_MAX_SHIFT = 30
+BG_POLICY_LOCAL = 2  # scg_bg_local_policy.kind
+BG_LOCAL_MAX_DELAY = 64
+BG_LOCAL_FEATURES = 4  # net, line, down, own (csrc/scg_bg_local.h)
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -117,6 +120,12 @@ BG_SERVER_ARGS_BYTES = 512
 
 class BgPolicy(ctypes.Structure):
     """scg_bg_policy (include/scgpu.h): the per-env linear policy of scg_bg_rollout_policy."""
+    _fields_ = [("kind", ctypes.c_int32), ("shift", ctypes.c_int32), ("act_lo", ctypes.c_int32),
+                ("act_hi", ctypes.c_int32), ("params", ctypes.c_void_p)]
+
+
+class BgLocalPolicy(ctypes.Structure):
+    """scg_bg_local_policy (include/scgpu.h): the local-information policy of scg_bg_rollout_local."""
     _fields_ = [("kind", ctypes.c_int32), ("shift", ctypes.c_int32), ("act_lo", ctypes.c_int32),
                 ("act_hi", ctypes.c_int32), ("params", ctypes.c_void_p)]
 
@@ -296,6 +305,11 @@ SIGNATURES = {
     "scg_bg_rollout_policy": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_int32,
                                              ctypes.POINTER(BgPolicy), ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "scg_bg_rollout_local": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_int32,
+                                            ctypes.POINTER(BgLocalPolicy), ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "scg_bg_local_features": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_void_p,
+                                             ctypes.c_void_p]),
     "scg_bg_poisson_demand": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState),
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_struct_sizes": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)] * 3),

@@ -111,6 +111,15 @@ class PackedPolicy:
         self.params, self.n_envs, self.levels = params, n_envs, levels
 
 
+class PackedLocalPolicy:
+    """Per-env local-information policy parameters as scg_bg_rollout_local reads them
+    (BeerGameVecEnv.pack_local_policy): `params` int32 [5*L, N] on the env's device."""
+    __slots__ = ("params", "n_envs", "levels")
+
+    def __init__(self, params, n_envs, levels):
+        self.params, self.n_envs, self.levels = params, n_envs, levels
+
+
 class PolicyRollout:
     """What BeerGameVecEnv.rollout_policy returns: `reward_sum` int64 [N], and `actions`
     [K, N, L], `obs` [K, N, L], `rewards` [K, N] (int32) where requested, else None."""
@@ -512,9 +521,27 @@ class BeerGameVecEnv:
         Returns a PolicyRollout: reward_sum int64 [N], the sum of the call's rewards per env
         (across auto-resets), and on request actions [K, N, L], obs [K, N, L], rewards [K, N].
         With weights = -g * I, bias = g * S and shift = log2 of the scale this is the smoothed
-        order-up-to rule on net stock."""
+        order-up-to rule on net stock.
+
+        With weights a pack_local_policy() result (and bias None) the policy is the
+        local-information one (scg_bg_rollout_local): each level l decides from four int32
+        about itself, for the state after week w of the episode and horizon T
+
+            net   inventory[l] - backlog[l] (+ max_stock for BeerGame2VecEnv): o[l] above
+            line  orders_placed[l] + (backlog[l+1] if l+1 < L else 0) + the shipments still to
+                  arrive at l in weeks w+1..T (the supply line)
+            down  orders_placed[l-1] for l >= 1; for l = 0 the customer demand of week w
+                  (initial_orders_value just after a reset)
+            own   orders_placed[l]
+
+            z[l] = bias[l] + weights[l] @ (net, line, down, own);  action as above
+
+        Shipments scheduled past week T are not in `line`: the kernels drop them, so they are
+        not in the state. weights[l] = (-1, -1, 0, 0), bias[l] = S is order-up-to S on the
+        inventory position (BeerGame2VecEnv: bias S + max_stock). Refused (ValueError): a
+        shipment delay above 64 and full_table envs. policy_features() returns the features."""
         N, L = self.n_envs, self.levels
-        if isinstance(weights, PackedPolicy):
+        if isinstance(weights, (PackedPolicy, PackedLocalPolicy)):
             if bias is not None:
                 raise ValueError("a packed policy carries its bias")
             packed = weights
@@ -538,11 +565,44 @@ class BeerGameVecEnv:
                             torch.empty((K, N, L), **i32) if return_actions else None,
                             torch.empty((K, N, L), **i32) if return_obs else None,
                             torch.empty((K, N), **i32) if return_rewards else None)
-        pol = nat.BgPolicy(nat.BG_POLICY_LINEAR, int(shift), lo, hi, packed.params.data_ptr())
-        nat.check(nat.lib.scg_bg_rollout_policy(self._cfg_ref, self._st_ref, int(n_weeks), ctypes.byref(pol),
-                                                nat.ptr(res.actions), nat.ptr(res.obs), nat.ptr(res.rewards),
-                                                res.reward_sum.data_ptr(), self._flags, self._stream()))
+        if isinstance(packed, PackedLocalPolicy):
+            pol = nat.BgLocalPolicy(nat.BG_POLICY_LOCAL, int(shift), lo, hi, packed.params.data_ptr())
+            entry = nat.lib.scg_bg_rollout_local
+        else:
+            pol = nat.BgPolicy(nat.BG_POLICY_LINEAR, int(shift), lo, hi, packed.params.data_ptr())
+            entry = nat.lib.scg_bg_rollout_policy
+        nat.check(entry(self._cfg_ref, self._st_ref, int(n_weeks), ctypes.byref(pol), nat.ptr(res.actions),
+                        nat.ptr(res.obs), nat.ptr(res.rewards), res.reward_sum.data_ptr(), self._flags, self._stream()))
         return res
+
+    def pack_local_policy(self, weights, bias):
+        """Per-env local-information policy parameters in the layout scg_bg_rollout_local reads:
+        int32 [5*L, N] on this env's device, word l*5+j of an env being weights[l][j] for j < 4
+        (net, line, down, own: see rollout_policy) and bias[l] for j == 4. weights is [N, L, 4]
+        or [L, 4], bias [N, L] or [L] (shared forms are broadcast); values must be exact int32.
+        Pass the result to rollout_policy(packed, None, n_weeks, ...)."""
+        N, L, F = self.n_envs, self.levels, nat.BG_LOCAL_FEATURES
+        if L > nat.BG_POLICY_MAX_LEVELS:
+            raise ValueError(f"rollout_policy supports up to {nat.BG_POLICY_MAX_LEVELS} levels, this env has {L}")
+        w = self._exact_int32("weights", weights, ((N, L, F), (L, F))).expand(N, L, F)
+        b = self._exact_int32("bias", bias, ((N, L), (L,))).expand(N, L)
+        words = torch.cat([w, b.unsqueeze(2)], dim=2).reshape(N, L * (F + 1))
+        return PackedLocalPolicy(words.t().contiguous(), N, L)
+
+    def policy_features(self, out=None):
+        """The local-information policy's features of the state as it stands (after reset(),
+        step(), rollout(), rollout_policy() or load_state_dict()): int32 [N, L, 4], per level
+        (net, line, down, own) as rollout_policy() defines them; shipments scheduled past the
+        last week are not in `line`. `out`, when given, is an int32 [N, L, 4] tensor on this
+        env's device and is returned. Refused as rollout_policy() refuses the local policy."""
+        shape = (self.n_envs, self.levels, nat.BG_LOCAL_FEATURES)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != self.device \
+                or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int32 {list(shape)} tensor on {self.device}")
+        nat.check(nat.lib.scg_bg_local_features(self._cfg_ref, self._st_ref, out.data_ptr(), self._stream()))
+        return out
 
     def poisson_demand(self, episode=None):
         """The Poisson demand [T, N] the kernels draw for `episode` (default: current)."""

@@ -52,7 +52,9 @@ extern "C" {
  *   scg_sc_rollout_mlp and scg_sc_mlp_fused (scg_sc_mlp: the same closed loop with a
  *   one-hidden-layer ReLU policy), added entry points; also scg_sc_rollout_sampled
  *   (scg_sc_sampling: either closed loop with the caller's noise added to the action before
- *   its clamp, for policy-gradient training), an added entry point. */
+ *   its clamp, for policy-gradient training), an added entry point; also scg_bg_rollout_local
+ *   and scg_bg_local_features (scg_bg_local_policy: the closed-loop BeerGame rollout with a
+ *   local-information policy on inventory position and orders), added entry points. */
 #define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
@@ -431,6 +433,49 @@ typedef struct scg_bg_policy {
 SCG_API int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks,
                                   const scg_bg_policy* policy, int32_t* actions_out, int32_t* obs,
                                   int32_t* rewards, int64_t* reward_sum, uint32_t flags, void* stream);
+
+/*
+ * The same closed loop with a local-information policy: each level decides from four int32
+ * about itself. For the state after week w of the current episode (w = 0: just reset), horizon
+ * T, level l of L, in the reference's attribute names:
+ *   f[l][0] net   inventory[l] - backlog[l] (+ max_stock for variant 2): scg_bg_rollout_policy's
+ *                 observation
+ *   f[l][1] line  the supply line: orders_placed[l] + (backlog[l+1] if l+1 < L else 0)
+ *                 + sum_{v=w+1..T} shipments[v][l]
+ *   f[l][2] down  the latest order from downstream: orders_placed[l-1] for l >= 1; for l = 0 the
+ *                 customer demand of week w, initial_orders_value at w = 0 (also after an
+ *                 auto-reset inside the call)
+ *   f[l][3] own   orders_placed[l]
+ * Shipments scheduled past week T are not in `line` (the kernels drop them: they are not in the
+ * state). Every feature is int32 in wrapping arithmetic and touches no overflow flag.
+ *   z_l = b_l + sum_{j<4} W[l][j] * f[l][j]        int64, two's-complement wrap
+ *   a_l = min(max(z_l >> shift, act_lo), act_hi)   arithmetic shift (floor), then the clamp
+ * (csrc/scg_bg_local.h is the one definition, host and device). W = (-1, -1, 0, 0), b = S is
+ * order-up-to S on the inventory position (variant 2: b = S + max_stock).
+ * The in-transit sum is taken once per launch over the ring rows the episode has scheduled (a
+ * mask the host derives from the delay list and st->week), then kept in registers; nothing is
+ * carried between launches or calls, so scg_bg_reset, scg_bg_step, scg_bg_rollout, this call and
+ * a restored state may precede it in any order.
+ * Buffers, flags, contract and error codes are scg_bg_rollout_policy's (kind must be
+ * SCG_BG_POLICY_LOCAL); SCG_ERR_INVALID also for a delay above SCG_BG_LOCAL_MAX_DELAY
+ * (shipment_delays[0..T] and, with stochastic_delays, delay_hi - 1) and for full_table configs.
+ *
+ * scg_bg_local_features writes the same four features of the state as it stands:
+ *   out DEVICE int32 [N][L][4]. The same checks, except that week == max_weeks is allowed.
+ */
+#define SCG_BG_POLICY_LOCAL 2
+#define SCG_BG_LOCAL_MAX_DELAY 64
+typedef struct scg_bg_local_policy {
+  int32_t kind;            /* SCG_BG_POLICY_LOCAL */
+  int32_t shift;           /* 0..30 */
+  int32_t act_lo, act_hi;
+  const int32_t* params;   /* DEVICE int32 [5*L][N], env fastest: word l*5+j is W[l][j] for j < 4, b[l] for j == 4 */
+} scg_bg_local_policy;
+
+SCG_API int scg_bg_rollout_local(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks,
+                                 const scg_bg_local_policy* policy, int32_t* actions_out, int32_t* obs,
+                                 int32_t* rewards, int64_t* reward_sum, uint32_t flags, void* stream);
+SCG_API int scg_bg_local_features(const scg_bg_config* cfg, const scg_bg_state* st, int32_t* out, void* stream);
 
 /*
  * Device-side Philox draws for tests and benchmarks (no host round trip):
