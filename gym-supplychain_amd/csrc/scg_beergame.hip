@@ -747,6 +747,52 @@ int scg_bg_rollout_local(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_w
   });
 }
 
+// ---- the float32 MLP policy on the local features (scg_bg_mlp.h) --------------------------
+int scg_bg_rollout_mlp(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_mlp* policy,
+                       int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum, uint32_t flags,
+                       void* stream) {
+  if (int rc = check_state(cfg, st)) return rc;
+  if (!policy || !policy->params) return fail(SCG_ERR_INVALID, "MLP policy rollout needs a policy with params");
+  if (policy->kind != SCG_BG_POLICY_MLP) return fail(SCG_ERR_INVALID, "unknown MLP policy kind %d", policy->kind);
+  if (!bg_mlp_valid(policy->kind, policy->hidden, policy->act_lo, policy->act_hi))
+    return fail(SCG_ERR_INVALID,
+                "MLP policy needs hidden in 1..%d and -2^24 <= act_lo <= act_hi <= 2^24 (got hidden=%d, clamp %d..%d)",
+                kBgMlpMaxHidden, policy->hidden, policy->act_lo, policy->act_hi);
+  if (!policy->noise != !policy->std) return fail(SCG_ERR_INVALID, "MLP policy: noise and std go together");
+  if (policy->samples_out && !policy->noise) return fail(SCG_ERR_INVALID, "MLP policy: samples_out needs noise and std");
+  if (int rc = check_local_config(cfg)) return rc;
+  if (n_weeks < 0) return fail(SCG_ERR_INVALID, "MLP policy rollout needs n_weeks >= 0");
+  if (int rc = check_step(cfg, st)) return rc;
+  if (int rc = check_horizon(cfg, st, n_weeks, flags)) return rc;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_weeks == 0) {  // no launch: the sum of no rewards
+    if (reward_sum && hipMemsetAsync(reward_sum, 0, static_cast<size_t>(st->n_envs) * sizeof(int64_t), s) != hipSuccess)
+      return fail(SCG_ERR_HIP, "hipMemsetAsync(reward_sum) failed");
+    return SCG_OK;
+  }
+  const int64_t stride = st->n_envs * cfg->levels;
+  return rollout_launches(cfg, st, n_weeks, flags, [&](int32_t done_k, int32_t K, const BgArgs& a, const RolloutWeeks& weeks) {
+    const int32_t w0 = st->week;  // the state this launch starts from (weeks.wk[0].week - 1)
+    MlpArgs ma;
+    ma.params = policy->params;
+    ma.acts_out = actions_out ? actions_out + done_k * stride : nullptr;
+    ma.obs_out = obs ? obs + done_k * stride : nullptr;
+    ma.rew_out = rewards ? rewards + done_k * st->n_envs : nullptr;
+    ma.reward_sum = reward_sum;
+    ma.std = policy->std;
+    ma.noise = policy->noise ? policy->noise + done_k * stride : nullptr;
+    ma.samples_out = policy->samples_out ? policy->samples_out + done_k * stride : nullptr;
+    ma.features_out = policy->features_out ? policy->features_out + done_k * stride * kLocalFeatures : nullptr;
+    ma.hidden = policy->hidden;
+    ma.lo = policy->act_lo;
+    ma.hi = policy->act_hi;
+    ma.first = done_k == 0;
+    ma.last_fixed = local_last_fixed(cfg, w0);
+    ma.live = local_mask(cfg, w0);
+    return bg_launch_mlp_rollout(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, ma);
+  });
+}
+
 int scg_bg_local_features(const scg_bg_config* cfg, const scg_bg_state* st, int32_t* out, void* stream) {
   if (int rc = check_state(cfg, st)) return rc;
   if (!out) return fail(SCG_ERR_INVALID, "local features: null output");

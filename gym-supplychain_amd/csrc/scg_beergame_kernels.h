@@ -4,7 +4,8 @@
 // L. scg_beergame.hip dispatches on L at run time; the launchers are instantiated in four
 // units (levels 1-4, 5-8, 9-12, 13-16) that compile in parallel. The closed-loop policy
 // rollout kernels (levels 1-8) are instantiated, with their launcher, in scg_bg_policy.hip
-// (linear policy) and scg_bg_local.hip (local-information policy).
+// (linear policy), scg_bg_local.hip (local-information policy) and scg_bg_mlp.hip (float32 MLP
+// policy on the local features).
 //
 // BeerGame hot path for gfx950: reset / step / rollout kernels + their C-ABI launchers.
 //
@@ -33,6 +34,7 @@
 #include <type_traits>
 
 #include "scg_bg_local.h"
+#include "scg_bg_mlp.h"
 #include "scg_bg_plan.h"
 #include "scg_bg_policy.h"
 #include "scg_common.h"
@@ -1000,6 +1002,7 @@ constexpr int kRolloutGroup = 8;
 struct RolloutActs {
   static constexpr bool kPolicy = false;
   static constexpr bool kLocal = false;
+  static constexpr bool kMlp = false;
   static constexpr int kGroup = kRolloutGroup;
   const int32_t* acts;  // [K][N][L] of this launch
   int32_t* obs_out;     // [K][N][L] or null
@@ -1016,6 +1019,7 @@ struct RolloutActs {
 struct PolicyArgs {
   static constexpr bool kPolicy = true;
   static constexpr bool kLocal = false;
+  static constexpr bool kMlp = false;
   static constexpr int kGroup = 1;
   const int32_t* params;  // [L*(L+1)][N]
   int32_t* acts_out;      // [K][N][L] of this launch, or null
@@ -1035,6 +1039,7 @@ struct PolicyArgs {
 struct LocalArgs {
   static constexpr bool kPolicy = true;
   static constexpr bool kLocal = true;
+  static constexpr bool kMlp = false;
   static constexpr int kGroup = 1;
   const int32_t* params;  // [5*L][N]
   int32_t* acts_out;      // [K][N][L] of this launch, or null
@@ -1045,6 +1050,33 @@ struct LocalArgs {
   int32_t first;          // the first launch of a call stores reward_sum, later ones add to it
   int32_t last_fixed;     // FIXED demand: customer_demand[w0 - 1] (unused at w0 = 0)
   uint64_t live;          // local_live_mask of the launch's first state
+};
+
+// Mlp: the closed loop with the float32 MLP policy on the local features (scg_bg_mlp.h). The
+// in-transit sums and the last demand are LocalArgs's; the parameters are one block shared by
+// every env, read with wave-uniform indices through the scalar cache each week, so no lane keeps
+// parameter registers: beside the state a lane holds the 4L inputs and the L sums. A launch
+// samples when `noise` is non-null (a uniform branch): week k's noise row, L floats per lane laid
+// out like an action row, is requested at the top of the week, before the features exist.
+// samples_out may be the noise buffer: a lane reads its row, then writes it.
+struct MlpArgs {
+  static constexpr bool kPolicy = true;
+  static constexpr bool kLocal = true;
+  static constexpr bool kMlp = true;
+  static constexpr int kGroup = 1;
+  const float* params;    // [Q] (scg_bg_mlp.h), shared
+  int32_t* acts_out;      // [K][N][L] of this launch, or null
+  int32_t* obs_out;       // [K][N][L] or null
+  int32_t* rew_out;       // [K][N] or null
+  int64_t* reward_sum;    // [N] or null
+  const float* std;       // [L]; non-null when noise is
+  const float* noise;     // [K][N][L] of this launch, or null: deterministic
+  float* samples_out;     // [K][N][L] of this launch (u), or null
+  int32_t* features_out;  // [K][N][L][4] of this launch, or null
+  int32_t hidden, lo, hi;
+  int32_t first;          // as LocalArgs
+  int32_t last_fixed;
+  uint64_t live;
 };
 
 // The sum of the ring rows `live` marks, from the state after week w0: transit[l] of
@@ -1093,8 +1125,13 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
   const int64_t row = n * L;
   const int64_t stride = a.n * L;
   constexpr bool kLocal = Source::kLocal;
+  constexpr bool kMlp = Source::kMlp;
   [[maybe_unused]] int32_t par[kLocal ? L * kLocalRow : L * (L + 1)];
-  if constexpr (kLocal)
+  [[maybe_unused]] float sd[L];
+  if constexpr (kMlp) {  // shared parameters stay in memory; the L standard deviations are uniform
+#pragma unroll
+    for (int l = 0; l < L; ++l) sd[l] = src.noise ? const_tab(src.std)[l] : 0.0f;
+  } else if constexpr (kLocal)
     local_load<L>(src.params, a.n, n, par);
   else if constexpr (Source::kPolicy)
     policy_load<L>(src.params, a.n, n, par);
@@ -1149,10 +1186,33 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
       }
       int32_t due[L], obs[L], ship[L], cur[L];
       int32_t(&act)[L] = group_act[u];
+      [[maybe_unused]] int32_t eps[L];  // the week's noise row, as bits
+      if constexpr (kMlp)
+        if (src.noise) load_row<L>(reinterpret_cast<const int32_t*>(src.noise) + k * stride + row, eps);
       if constexpr (Source::kPolicy) {
         int32_t o[L];
         policy_obs<L>(inv, bk, kV2 ? a.max_stock : 0, o);
-        if constexpr (kLocal) {
+        if constexpr (kMlp) {
+          int32_t f[L][kLocalFeatures];
+          local_features<L>(o, bk, op, transit, last_demand, f);
+          if (src.features_out) {
+#pragma unroll
+            for (int l = 0; l < L; ++l) store_row<kLocalFeatures>(src.features_out + (k * stride + row + l) * kLocalFeatures, f[l]);
+          }
+          float z[L];
+          bg_mlp_z<L>(const_tab(src.params), src.hidden, f, z);
+          if (src.noise) {
+            int32_t ubits[L];
+#pragma unroll
+            for (int l = 0; l < L; ++l) {
+              z[l] = bg_mlp_sample(z[l], sd[l], __int_as_float(eps[l]));
+              ubits[l] = __float_as_int(z[l]);
+            }
+            if (src.samples_out) store_row<L>(reinterpret_cast<int32_t*>(src.samples_out) + k * stride + row, ubits);
+          }
+#pragma unroll
+          for (int l = 0; l < L; ++l) act[l] = bg_mlp_finish(z[l], src.lo, src.hi);
+        } else if constexpr (kLocal) {
           int32_t f[L][kLocalFeatures];
           local_features<L>(o, bk, op, transit, last_demand, f);
           local_act<L>(par, f, src.clamp, act);
@@ -1297,6 +1357,10 @@ int bg_launch_local_rollout(int L, int variant, dim3 grid, hipStream_t s, const 
                             const RolloutWeeks& weeks, const LocalArgs& la);
 int bg_launch_local_features(dim3 grid, hipStream_t s, const BgArgs& a, int32_t L, int32_t w0, uint64_t live,
                              int32_t last_fixed, int32_t* out);
+
+// The same for the float32 MLP policy; defined in scg_bg_mlp.hip.
+int bg_launch_mlp_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
+                          const RolloutWeeks& weeks, const MlpArgs& ma);
 
 // hipModuleLaunchKernel with the kernel's function handle resolved once per instantiation,
 // skipping the host-stub lookup of hipLaunchKernel on every step: ≈0.5 µs less host time

@@ -130,6 +130,18 @@ class BgLocalPolicy(ctypes.Structure):
                 ("act_hi", ctypes.c_int32), ("params", ctypes.c_void_p)]
 
 
+BG_POLICY_MLP = 3  # scg_bg_mlp.kind
+BG_MLP_MAX_HIDDEN = 64
+BG_MLP_MAX_BOUND = 1 << 24  # |act_lo|, |act_hi| up to here: exact as float32
+
+
+class BgMlp(ctypes.Structure):
+    """scg_bg_mlp (include/scgpu.h): the shared float32 MLP policy of scg_bg_rollout_mlp."""
+    _fields_ = [("kind", ctypes.c_int32), ("hidden", ctypes.c_int32), ("act_lo", ctypes.c_int32),
+                ("act_hi", ctypes.c_int32), ("params", ctypes.c_void_p), ("std", ctypes.c_void_p),
+                ("noise", ctypes.c_void_p), ("samples_out", ctypes.c_void_p), ("features_out", ctypes.c_void_p)]
+
+
 SC_POLICY_LINEAR = 1
 
 
@@ -310,6 +322,9 @@ SIGNATURES = {
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "scg_bg_local_features": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_void_p,
                                              ctypes.c_void_p]),
+    "scg_bg_rollout_mlp": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_int32,
+                                          ctypes.POINTER(BgMlp), ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "scg_bg_poisson_demand": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState),
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_struct_sizes": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)] * 3),

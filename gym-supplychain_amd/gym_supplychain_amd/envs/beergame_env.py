@@ -26,6 +26,7 @@ from .. import checkpoint as ckpt
 from .. import spaces
 from . import resident
 from .step_server import _ResidentServer
+from .supplychain_env import SupplyChainVecEnv, pack_mlp_words
 from ..distributed import entropy_seed
 
 # beergame_env.py:16-23
@@ -120,13 +121,26 @@ class PackedLocalPolicy:
         self.params, self.n_envs, self.levels = params, n_envs, levels
 
 
+class PackedLocalMlp:
+    """One shared float32 MLP policy over the local features as scg_bg_rollout_mlp reads it
+    (BeerGameVecEnv.pack_local_mlp): `params` float32 [Q] on the env's device."""
+    __slots__ = ("params", "n_envs", "levels", "hidden")
+
+    def __init__(self, params, n_envs, levels, hidden):
+        self.params, self.n_envs, self.levels, self.hidden = params, n_envs, levels, hidden
+
+
 class PolicyRollout:
     """What BeerGameVecEnv.rollout_policy returns: `reward_sum` int64 [N], and `actions`
-    [K, N, L], `obs` [K, N, L], `rewards` [K, N] (int32) where requested, else None."""
-    __slots__ = ("reward_sum", "actions", "obs", "rewards")
+    [K, N, L], `obs` [K, N, L], `rewards` [K, N] (int32) where requested, else None. With a
+    pack_local_mlp() policy also `samples` float32 [K, N, L] (the samples_out tensor of a sampled
+    call: the actions before rounding and clamp) and `features` int32 [K, N, L, 4] (what each
+    week's action was computed from), each where requested, else None."""
+    __slots__ = ("reward_sum", "actions", "obs", "rewards", "samples", "features")
 
-    def __init__(self, reward_sum, actions=None, obs=None, rewards=None):
+    def __init__(self, reward_sum, actions=None, obs=None, rewards=None, samples=None, features=None):
         self.reward_sum, self.actions, self.obs, self.rewards = reward_sum, actions, obs, rewards
+        self.samples, self.features = samples, features
 
 
 class BeerGameVecEnv:
@@ -508,7 +522,8 @@ class BeerGameVecEnv:
         return PackedPolicy(words.t().contiguous(), N, L)
 
     def rollout_policy(self, weights, bias=None, n_weeks=None, shift=0, clip=None, return_actions=False,
-                       return_obs=False, return_rewards=False):
+                       return_obs=False, return_rewards=False, noise=None, std=None, samples_out=None,
+                       return_features=False):
         """n_weeks weeks in as few launches as possible with every env's action computed on the
         device from its own last observation o (what reset() or the previous step returned):
 
@@ -539,9 +554,26 @@ class BeerGameVecEnv:
         Shipments scheduled past week T are not in `line`: the kernels drop them, so they are
         not in the state. weights[l] = (-1, -1, 0, 0), bias[l] = S is order-up-to S on the
         inventory position (BeerGame2VecEnv: bias S + max_stock). Refused (ValueError): a
-        shipment delay above 64 and full_table envs. policy_features() returns the features."""
+        shipment delay above 64 and full_table envs. policy_features() returns the features.
+
+        With weights a pack_local_mlp() result (and bias None) the policy is one float32 network
+        shared by every env (scg_bg_rollout_mlp), over the same features as x[l*4+j] =
+        float32(feature j of level l), every multiply and add rounded to float32 on its own:
+
+            z = b2;  for i in range(H):  h = b1[i];  for j in range(4L): h = h + w1[i][j] * x[j]
+                                         h = h if h > 0 else 0;  for a in range(L): z[a] = z[a] + w2[a][i] * h
+            u = z                       (noise None: deterministic)
+            u = z + std * noise[k]      (sampled; the product is rounded first)
+            action = lo if not u >= lo else (hi if u >= hi else round-half-even(u))
+
+        shift must be 0; clip (lo, hi) within +-2**24, None for (0, max_order) on BeerGame2VecEnv
+        (ValueError on BeerGameVecEnv, whose default is the int32 range). noise float32 [K, N, L]
+        and std (a float or [L], finite, >= 0) go together; samples_out float32 [K, N, L]
+        receives u and may be the noise tensor itself; return_features=True returns the int32
+        [K, N, L, 4] features each week's action was computed from. The result's `samples` and
+        `features` carry them. With an integer policy these four arguments raise ValueError."""
         N, L = self.n_envs, self.levels
-        if isinstance(weights, (PackedPolicy, PackedLocalPolicy)):
+        if isinstance(weights, (PackedPolicy, PackedLocalPolicy, PackedLocalMlp)):
             if bias is not None:
                 raise ValueError("a packed policy carries its bias")
             packed = weights
@@ -560,12 +592,31 @@ class BeerGameVecEnv:
         if lo > hi:
             raise ValueError(f"clip=({lo}, {hi}) is empty")
         K = max(int(n_weeks), 0)
+        mlp = isinstance(packed, PackedLocalMlp)
+        if not mlp and (noise is not None or std is not None or samples_out is not None or return_features):
+            raise ValueError("noise, std, samples_out and return_features need a pack_local_mlp() policy")
+        if mlp:
+            if shift != 0:
+                raise ValueError(f"a pack_local_mlp() policy takes no shift, got {shift!r}")
+            if lo < -nat.BG_MLP_MAX_BOUND or hi > nat.BG_MLP_MAX_BOUND:
+                raise ValueError(f"a pack_local_mlp() policy needs clip within +-2**24, got ({lo}, {hi})" +
+                                 (": pass clip=(lo, hi)" if clip is None else ""))
+            sd = None
+            if noise is not None or std is not None or samples_out is not None:
+                noise, sd, samples_out = self._sampling(K, noise, std, samples_out)
         i32 = dict(dtype=torch.int32, device=self.device)
         res = PolicyRollout(torch.empty(N, dtype=torch.int64, device=self.device),
                             torch.empty((K, N, L), **i32) if return_actions else None,
                             torch.empty((K, N, L), **i32) if return_obs else None,
                             torch.empty((K, N), **i32) if return_rewards else None)
-        if isinstance(packed, PackedLocalPolicy):
+        if mlp:
+            res.samples = samples_out
+            res.features = torch.empty((K, N, L, nat.BG_LOCAL_FEATURES), **i32) if return_features else None
+            bufs = (sd, noise, samples_out, res.features) if K else (None,) * 4  # no weeks: empty tensors, no pointers
+            pol = nat.BgMlp(nat.BG_POLICY_MLP, packed.hidden, lo, hi, packed.params.data_ptr(),
+                            *(None if t is None else t.data_ptr() for t in bufs))
+            entry = nat.lib.scg_bg_rollout_mlp
+        elif isinstance(packed, PackedLocalPolicy):
             pol = nat.BgLocalPolicy(nat.BG_POLICY_LOCAL, int(shift), lo, hi, packed.params.data_ptr())
             entry = nat.lib.scg_bg_rollout_local
         else:
@@ -588,6 +639,61 @@ class BeerGameVecEnv:
         b = self._exact_int32("bias", bias, ((N, L), (L,))).expand(N, L)
         words = torch.cat([w, b.unsqueeze(2)], dim=2).reshape(N, L * (F + 1))
         return PackedLocalPolicy(words.t().contiguous(), N, L)
+
+    _exact_f32 = SupplyChainVecEnv._exact_f32  # float32 on this env's device, exactly or ValueError
+
+    def pack_local_mlp(self, w1, b1, w2, b2):
+        """One-hidden-layer ReLU policy parameters over the local features in the layout
+        scg_bg_rollout_mlp reads: float32 [Q] on this env's device, one network for every env.
+        w1 [H, 4L], b1 [H], w2 [L, H], b2 [L]: the layout of torch.nn.Linear.weight / .bias, input
+        l*4+j being feature j (net, line, down, own) of level l. Q = H*(4L+1) + L*(H+1): word
+        i*(4L+1)+j is w1[i][j] (j < 4L) or b1[i] (j == 4L), word H*(4L+1) + a*(H+1) + i is w2[a][i]
+        (i < H) or b2[a] (i == H). H comes from the shapes (1..64). Values must be exactly
+        representable as float32. ValueError otherwise, and for per-env shapes ([N, ...]): the
+        network is shared; populations of per-env parameters are what pack_local_policy() serves.
+        Pass the result to rollout_policy(packed, None, n_weeks, ...)."""
+        N, L = self.n_envs, self.levels
+        if L > nat.BG_POLICY_MAX_LEVELS:
+            raise ValueError(f"rollout_policy supports up to {nat.BG_POLICY_MAX_LEVELS} levels, this env has {L}")
+        I = L * nat.BG_LOCAL_FEATURES
+        shape = tuple(w1.shape) if hasattr(w1, "shape") else tuple(np.shape(w1))
+        if len(shape) == 3:
+            raise ValueError(f"per-env networks are not supported: w1 must have shape [H, {I}], got {list(shape)}")
+        if len(shape) != 2 or shape[1] != I:
+            raise ValueError(f"w1 must have shape [H, {I}], got {list(shape)}")
+        H = int(shape[0])
+        if not 1 <= H <= nat.BG_MLP_MAX_HIDDEN:
+            raise ValueError(f"the hidden width must be in 1..{nat.BG_MLP_MAX_HIDDEN}, got {H}")
+        w1 = self._exact_f32("w1", w1, ((H, I),))
+        b1 = self._exact_f32("b1", b1, ((H,),))
+        w2 = self._exact_f32("w2", w2, ((L, H),))
+        b2 = self._exact_f32("b2", b2, ((L,),))
+        return PackedLocalMlp(pack_mlp_words(w1, b1, w2, b2), N, L, H)
+
+    def _sampling(self, K, noise, std, samples_out):
+        """The checked (noise, std on the device, samples_out) of a sampled rollout_policy call."""
+        N, L = self.n_envs, self.levels
+        if noise is None or std is None:
+            raise ValueError("noise and std go together" if noise is not None or std is not None else
+                             "samples_out needs noise and std")
+        for name, x in (("noise", noise), ("samples_out", samples_out)):
+            if x is None:
+                continue
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != self.device or \
+                    tuple(x.shape) != (K, N, L) or not x.is_contiguous() or x.data_ptr() % 16:
+                raise ValueError(f"{name} must be a contiguous, 16-byte aligned float32 tensor [{K}, {N}, {L}] on "
+                                 f"{self.device}")
+        try:
+            sd = torch.as_tensor(std, dtype=torch.float32).detach().to(self.device)
+        except (TypeError, RuntimeError) as e:
+            raise ValueError(f"std must be a float or float32 [{L}]: {e}") from None
+        if sd.dim() == 0:
+            sd = sd.expand(L)
+        if tuple(sd.shape) != (L,):
+            raise ValueError(f"std must be a float or have shape [{L}], got {list(sd.shape)}")
+        if not bool((torch.isfinite(sd) & (sd >= 0)).all()):  # the call's one host read
+            raise ValueError("std must be finite and >= 0")
+        return noise, sd.contiguous(), samples_out
 
     def policy_features(self, out=None):
         """The local-information policy's features of the state as it stands (after reset(),

@@ -54,7 +54,10 @@ extern "C" {
  *   (scg_sc_sampling: either closed loop with the caller's noise added to the action before
  *   its clamp, for policy-gradient training), an added entry point; also scg_bg_rollout_local
  *   and scg_bg_local_features (scg_bg_local_policy: the closed-loop BeerGame rollout with a
- *   local-information policy on inventory position and orders), added entry points. */
+ *   local-information policy on inventory position and orders), added entry points; also
+ *   scg_bg_rollout_mlp (scg_bg_mlp: the same closed loop with a shared one-hidden-layer ReLU
+ *   policy in float32 over the local features, deterministic or sampled from the caller's
+ *   noise), an added entry point. */
 #define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
@@ -476,6 +479,53 @@ SCG_API int scg_bg_rollout_local(const scg_bg_config* cfg, scg_bg_state* st, int
                                  const scg_bg_local_policy* policy, int32_t* actions_out, int32_t* obs,
                                  int32_t* rewards, int64_t* reward_sum, uint32_t flags, void* stream);
 SCG_API int scg_bg_local_features(const scg_bg_config* cfg, const scg_bg_state* st, int32_t* out, void* stream);
+
+/*
+ * The same closed loop with a one-hidden-layer ReLU policy in float32 over the local features,
+ * one network shared by every env. With f[l][j] the int32 features above of the state the env
+ * stands in (after an auto-reset inside the call: the reset state's), x[l*4+j] = (float)f[l][j]
+ * (round to nearest even, exact below 2^24), I = 4L and H = hidden:
+ *   z_a = b2_a                                   a < L
+ *   for i = 0 .. H-1 ascending:
+ *       h = b1_i;  for j = 0 .. I-1 ascending:  h = h + W1[i][j] * x_j
+ *       h = (h > 0) ? h : +0.0f
+ *       for a < L:  z_a = z_a + W2[a][i] * h
+ *   u_a   = z_a                                   noise == NULL: deterministic
+ *   u_a   = z_a + (std_a * noise[k][n][a])        sampled; the product is rounded first
+ *   act_a = !(u_a >= (float)act_lo) ? act_lo : (u_a >= (float)act_hi ? act_hi : (int32)rintf(u_a))
+ * Every multiply and every add is rounded to float32 on its own, rintf rounds ties to even, a
+ * NaN u gives act_lo; k is the week's index in the call (csrc/scg_bg_mlp.h is the one
+ * definition, host and device).
+ *   params DEVICE float32 [Q], Q = H*(I+1) + L*(H+1): word i*(I+1)+j is W1[i][j] for j < I and
+ *     b1[i] for j == I; word H*(I+1) + a*(H+1) + i is W2[a][i] for i < H and b2[a] for i == H
+ *     (the layout of scg_sc_mlp with O = I and A = L). There is no per-env form.
+ *   std DEVICE float32 [L];  noise DEVICE float32 [K][N][L], both or neither;
+ *   samples_out DEVICE float32 [K][N][L] or NULL: u; it may be `noise` itself (each element is
+ *     read, then written, by one thread). Only with noise.
+ *   features_out DEVICE int32 [K][N][L][4] or NULL: the features week k's action was computed
+ *     from (what a trainer needs to recompute z with gradients).
+ * actions_out, obs, rewards, reward_sum, flags, the launch cut, the contract and the error codes
+ * are scg_bg_rollout_local's. SCG_ERR_INVALID, before any HIP call, also for: kind other than
+ * SCG_BG_POLICY_MLP, hidden outside 1..SCG_BG_MLP_MAX_HIDDEN, act_lo or act_hi outside
+ * [-2^24, 2^24] (so that both are exact as float32) or act_lo > act_hi, NULL params, noise
+ * without std or std without noise, samples_out without noise.
+ */
+#define SCG_BG_POLICY_MLP 3
+#define SCG_BG_MLP_MAX_HIDDEN 64
+typedef struct scg_bg_mlp {
+  int32_t kind;            /* SCG_BG_POLICY_MLP */
+  int32_t hidden;          /* 1 .. SCG_BG_MLP_MAX_HIDDEN */
+  int32_t act_lo, act_hi;  /* within [-2^24, 2^24] */
+  const float* params;     /* DEVICE float32 [Q], shared */
+  const float* std;        /* DEVICE float32 [L], or NULL */
+  const float* noise;      /* DEVICE float32 [K][N][L], or NULL: deterministic */
+  float* samples_out;      /* DEVICE float32 [K][N][L], or NULL */
+  int32_t* features_out;   /* DEVICE int32 [K][N][L][4], or NULL */
+} scg_bg_mlp;              /* 56 bytes, params at 16 */
+
+SCG_API int scg_bg_rollout_mlp(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_mlp* policy,
+                               int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum,
+                               uint32_t flags, void* stream);
 
 /*
  * Device-side Philox draws for tests and benchmarks (no host round trip):
