@@ -651,41 +651,7 @@ int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, 
   });
 }
 
-int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_policy* policy,
-                          int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum, uint32_t flags,
-                          void* stream) {
-  if (int rc = check_state(cfg, st)) return rc;
-  if (!policy || !policy->params) return fail(SCG_ERR_INVALID, "policy rollout needs a policy with params");
-  if (policy->kind != SCG_BG_POLICY_LINEAR) return fail(SCG_ERR_INVALID, "unknown policy kind %d", policy->kind);
-  if (!policy_valid(policy->kind, policy->shift, policy->act_lo, policy->act_hi))
-    return fail(SCG_ERR_INVALID, "policy needs shift in 0..%d and act_lo <= act_hi (got shift=%d, clamp %d..%d)",
-                kPolicyMaxShift, policy->shift, policy->act_lo, policy->act_hi);
-  if (cfg->levels > SCG_BG_POLICY_MAX_LEVELS)
-    return fail(SCG_ERR_INVALID, "policy rollout: levels=%d above %d", cfg->levels, SCG_BG_POLICY_MAX_LEVELS);
-  if (n_weeks < 0) return fail(SCG_ERR_INVALID, "policy rollout needs n_weeks >= 0");
-  if (int rc = check_step(cfg, st)) return rc;
-  if (int rc = check_horizon(cfg, st, n_weeks, flags)) return rc;
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n_weeks == 0) {  // no launch: the sum of no rewards
-    if (reward_sum && hipMemsetAsync(reward_sum, 0, static_cast<size_t>(st->n_envs) * sizeof(int64_t), s) != hipSuccess)
-      return fail(SCG_ERR_HIP, "hipMemsetAsync(reward_sum) failed");
-    return SCG_OK;
-  }
-  const int64_t stride = st->n_envs * cfg->levels;
-  return rollout_launches(cfg, st, n_weeks, flags, [&](int32_t done_k, int32_t K, const BgArgs& a, const RolloutWeeks& weeks) {
-    PolicyArgs pa;
-    pa.params = policy->params;
-    pa.acts_out = actions_out ? actions_out + done_k * stride : nullptr;
-    pa.obs_out = obs ? obs + done_k * stride : nullptr;
-    pa.rew_out = rewards ? rewards + done_k * st->n_envs : nullptr;
-    pa.reward_sum = reward_sum;
-    pa.clamp = PolicyClamp{policy->shift, policy->act_lo, policy->act_hi};
-    pa.first = done_k == 0;
-    return bg_launch_policy_rollout(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, pa);
-  });
-}
-
-// ---- the local-information policy (scg_bg_local.h) ---------------------------------------
+// ---- the closed loop: scg_bg_rollout_policy, _local and _mlp ------------------------------
 // What the in-transit sum needs of a config: every delay within the 64-bit live mask, and the
 // ring (a full table keeps rows past T, which would need a different rule).
 static int check_local_config(const scg_bg_config* cfg) {
@@ -711,17 +677,25 @@ static int32_t local_last_fixed(const scg_bg_config* cfg, int32_t w0) {
   return (cfg->demand_mode == SCG_DEMAND_FIXED && w0 >= 1) ? cfg->customer_demand[w0 - 1] : 0;
 }
 
-int scg_bg_rollout_local(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_local_policy* policy,
-                         int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum, uint32_t flags,
-                         void* stream) {
+// The one host path of the three entry points. `who` names the policy in the messages; validate()
+// checks what is particular to the policy struct; fill(src, done) sets what is particular to the
+// source, for the launch that starts `done` action words into the call's per-week buffers. The
+// order of the checks is behaviour (tests/test_bg_closed_abi.py).
+extern "C++" {
+template <class Source, class Policy, class Validate, class Fill>
+static int closed_rollout(const char* who, int32_t kind, const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks,
+                          const Policy* policy, int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum,
+                          uint32_t flags, void* stream, Validate&& validate, Fill&& fill) {
   if (int rc = check_state(cfg, st)) return rc;
-  if (!policy || !policy->params) return fail(SCG_ERR_INVALID, "local policy rollout needs a policy with params");
-  if (policy->kind != SCG_BG_POLICY_LOCAL) return fail(SCG_ERR_INVALID, "unknown local policy kind %d", policy->kind);
-  if (!local_valid(policy->kind, policy->shift, policy->act_lo, policy->act_hi))
-    return fail(SCG_ERR_INVALID, "local policy needs shift in 0..%d and act_lo <= act_hi (got shift=%d, clamp %d..%d)",
-                kPolicyMaxShift, policy->shift, policy->act_lo, policy->act_hi);
-  if (int rc = check_local_config(cfg)) return rc;
-  if (n_weeks < 0) return fail(SCG_ERR_INVALID, "local policy rollout needs n_weeks >= 0");
+  if (!policy || !policy->params) return fail(SCG_ERR_INVALID, "%s rollout needs a policy with params", who);
+  if (policy->kind != kind) return fail(SCG_ERR_INVALID, "unknown %s kind %d", who, policy->kind);
+  if (int rc = validate()) return rc;
+  if constexpr (Source::kLocal) {
+    if (int rc = check_local_config(cfg)) return rc;
+  } else if (cfg->levels > SCG_BG_POLICY_MAX_LEVELS) {
+    return fail(SCG_ERR_INVALID, "%s rollout: levels=%d above %d", who, cfg->levels, SCG_BG_POLICY_MAX_LEVELS);
+  }
+  if (n_weeks < 0) return fail(SCG_ERR_INVALID, "%s rollout needs n_weeks >= 0", who);
   if (int rc = check_step(cfg, st)) return rc;
   if (int rc = check_horizon(cfg, st, n_weeks, flags)) return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -732,65 +706,74 @@ int scg_bg_rollout_local(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_w
   }
   const int64_t stride = st->n_envs * cfg->levels;
   return rollout_launches(cfg, st, n_weeks, flags, [&](int32_t done_k, int32_t K, const BgArgs& a, const RolloutWeeks& weeks) {
-    const int32_t w0 = st->week;  // the state this launch starts from (weeks.wk[0].week - 1)
-    LocalArgs la;
-    la.params = policy->params;
-    la.acts_out = actions_out ? actions_out + done_k * stride : nullptr;
-    la.obs_out = obs ? obs + done_k * stride : nullptr;
-    la.rew_out = rewards ? rewards + done_k * st->n_envs : nullptr;
-    la.reward_sum = reward_sum;
-    la.clamp = PolicyClamp{policy->shift, policy->act_lo, policy->act_hi};
-    la.first = done_k == 0;
-    la.last_fixed = local_last_fixed(cfg, w0);
-    la.live = local_mask(cfg, w0);
-    return bg_launch_local_rollout(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, la);
+    const int64_t done = done_k * stride;
+    Source src;
+    src.params = policy->params;
+    src.acts_out = actions_out ? actions_out + done : nullptr;
+    src.obs_out = obs ? obs + done : nullptr;
+    src.rew_out = rewards ? rewards + done_k * st->n_envs : nullptr;
+    src.reward_sum = reward_sum;
+    src.first = done_k == 0;
+    if constexpr (Source::kLocal)  // st->week: the state this launch starts from (weeks.wk[0].week - 1)
+      src.start = LocalStart{local_last_fixed(cfg, st->week), local_mask(cfg, st->week)};
+    fill(src, done);
+    return bg_launch_closed(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, src);
   });
 }
 
-// ---- the float32 MLP policy on the local features (scg_bg_mlp.h) --------------------------
+// The two integer policies: beside the parameters, the shift and the clamp.
+template <class Source, class Policy>
+static int int_policy_rollout(const char* who, int32_t kind, const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks,
+                              const Policy* p, int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum,
+                              uint32_t flags, void* stream) {
+  return closed_rollout<Source>(
+      who, kind, cfg, st, n_weeks, p, actions_out, obs, rewards, reward_sum, flags, stream,
+      [&]() -> int {
+        if (clamp_valid(p->shift, p->act_lo, p->act_hi)) return SCG_OK;
+        return fail(SCG_ERR_INVALID, "%s needs shift in 0..%d and act_lo <= act_hi (got shift=%d, clamp %d..%d)", who,
+                    kPolicyMaxShift, p->shift, p->act_lo, p->act_hi);
+      },
+      [&](Source& src, int64_t) { src.clamp = PolicyClamp{p->shift, p->act_lo, p->act_hi}; });
+}
+}  // extern "C++"
+
+int scg_bg_rollout_policy(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_policy* policy,
+                          int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum, uint32_t flags,
+                          void* stream) {
+  return int_policy_rollout<PolicyArgs>("policy", SCG_BG_POLICY_LINEAR, cfg, st, n_weeks, policy, actions_out, obs, rewards,
+                                        reward_sum, flags, stream);
+}
+
+int scg_bg_rollout_local(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_local_policy* policy,
+                         int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum, uint32_t flags,
+                         void* stream) {
+  return int_policy_rollout<LocalArgs>("local policy", SCG_BG_POLICY_LOCAL, cfg, st, n_weeks, policy, actions_out, obs,
+                                       rewards, reward_sum, flags, stream);
+}
+
 int scg_bg_rollout_mlp(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_mlp* policy,
                        int32_t* actions_out, int32_t* obs, int32_t* rewards, int64_t* reward_sum, uint32_t flags,
                        void* stream) {
-  if (int rc = check_state(cfg, st)) return rc;
-  if (!policy || !policy->params) return fail(SCG_ERR_INVALID, "MLP policy rollout needs a policy with params");
-  if (policy->kind != SCG_BG_POLICY_MLP) return fail(SCG_ERR_INVALID, "unknown MLP policy kind %d", policy->kind);
-  if (!bg_mlp_valid(policy->kind, policy->hidden, policy->act_lo, policy->act_hi))
-    return fail(SCG_ERR_INVALID,
-                "MLP policy needs hidden in 1..%d and -2^24 <= act_lo <= act_hi <= 2^24 (got hidden=%d, clamp %d..%d)",
-                kBgMlpMaxHidden, policy->hidden, policy->act_lo, policy->act_hi);
-  if (!policy->noise != !policy->std) return fail(SCG_ERR_INVALID, "MLP policy: noise and std go together");
-  if (policy->samples_out && !policy->noise) return fail(SCG_ERR_INVALID, "MLP policy: samples_out needs noise and std");
-  if (int rc = check_local_config(cfg)) return rc;
-  if (n_weeks < 0) return fail(SCG_ERR_INVALID, "MLP policy rollout needs n_weeks >= 0");
-  if (int rc = check_step(cfg, st)) return rc;
-  if (int rc = check_horizon(cfg, st, n_weeks, flags)) return rc;
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n_weeks == 0) {  // no launch: the sum of no rewards
-    if (reward_sum && hipMemsetAsync(reward_sum, 0, static_cast<size_t>(st->n_envs) * sizeof(int64_t), s) != hipSuccess)
-      return fail(SCG_ERR_HIP, "hipMemsetAsync(reward_sum) failed");
-    return SCG_OK;
-  }
-  const int64_t stride = st->n_envs * cfg->levels;
-  return rollout_launches(cfg, st, n_weeks, flags, [&](int32_t done_k, int32_t K, const BgArgs& a, const RolloutWeeks& weeks) {
-    const int32_t w0 = st->week;  // the state this launch starts from (weeks.wk[0].week - 1)
-    MlpArgs ma;
-    ma.params = policy->params;
-    ma.acts_out = actions_out ? actions_out + done_k * stride : nullptr;
-    ma.obs_out = obs ? obs + done_k * stride : nullptr;
-    ma.rew_out = rewards ? rewards + done_k * st->n_envs : nullptr;
-    ma.reward_sum = reward_sum;
-    ma.std = policy->std;
-    ma.noise = policy->noise ? policy->noise + done_k * stride : nullptr;
-    ma.samples_out = policy->samples_out ? policy->samples_out + done_k * stride : nullptr;
-    ma.features_out = policy->features_out ? policy->features_out + done_k * stride * kLocalFeatures : nullptr;
-    ma.hidden = policy->hidden;
-    ma.lo = policy->act_lo;
-    ma.hi = policy->act_hi;
-    ma.first = done_k == 0;
-    ma.last_fixed = local_last_fixed(cfg, w0);
-    ma.live = local_mask(cfg, w0);
-    return bg_launch_mlp_rollout(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, ma);
-  });
+  return closed_rollout<MlpArgs>(
+      "MLP policy", SCG_BG_POLICY_MLP, cfg, st, n_weeks, policy, actions_out, obs, rewards, reward_sum, flags, stream,
+      [&]() -> int {
+        if (!bg_mlp_valid(policy->kind, policy->hidden, policy->act_lo, policy->act_hi))
+          return fail(SCG_ERR_INVALID,
+                      "MLP policy needs hidden in 1..%d and -2^24 <= act_lo <= act_hi <= 2^24 (got hidden=%d, clamp %d..%d)",
+                      kBgMlpMaxHidden, policy->hidden, policy->act_lo, policy->act_hi);
+        if (!policy->noise != !policy->std) return fail(SCG_ERR_INVALID, "MLP policy: noise and std go together");
+        if (policy->samples_out && !policy->noise) return fail(SCG_ERR_INVALID, "MLP policy: samples_out needs noise and std");
+        return SCG_OK;
+      },
+      [&](MlpArgs& ma, int64_t done) {
+        ma.std = policy->std;
+        ma.noise = policy->noise ? policy->noise + done : nullptr;
+        ma.samples_out = policy->samples_out ? policy->samples_out + done : nullptr;
+        ma.features_out = policy->features_out ? policy->features_out + done * kLocalFeatures : nullptr;
+        ma.hidden = policy->hidden;
+        ma.lo = policy->act_lo;
+        ma.hi = policy->act_hi;
+      });
 }
 
 int scg_bg_local_features(const scg_bg_config* cfg, const scg_bg_state* st, int32_t* out, void* stream) {

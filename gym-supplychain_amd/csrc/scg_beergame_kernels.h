@@ -3,9 +3,9 @@
 // rollout kernels, templated on the level count L, and one launcher per kernel family and
 // L. scg_beergame.hip dispatches on L at run time; the launchers are instantiated in four
 // units (levels 1-4, 5-8, 9-12, 13-16) that compile in parallel. The closed-loop policy
-// rollout kernels (levels 1-8) are instantiated, with their launcher, in scg_bg_policy.hip
-// (linear policy), scg_bg_local.hip (local-information policy) and scg_bg_mlp.hip (float32 MLP
-// policy on the local features).
+// rollout kernels (levels 1-8) are instantiated through one launcher, bg_launch_closed, in
+// scg_bg_policy.hip (linear policy), scg_bg_local.hip (local-information policy) and
+// scg_bg_mlp.hip (float32 MLP policy on the local features).
 //
 // BeerGame hot path for gfx950: reset / step / rollout kernels + their C-ABI launchers.
 //
@@ -1002,82 +1002,111 @@ constexpr int kRolloutGroup = 8;
 struct RolloutActs {
   static constexpr bool kPolicy = false;
   static constexpr bool kLocal = false;
-  static constexpr bool kMlp = false;
   static constexpr int kGroup = kRolloutGroup;
+  template <int L>
+  struct Regs {};
   const int32_t* acts;  // [K][N][L] of this launch
   int32_t* obs_out;     // [K][N][L] or null
   int32_t* rew_out;     // [K][N] or null
 };
 
-// Policy: the closed loop. Each lane loads its L*(L+1) parameter words once per launch (word q
-// of a wave's 64 envs is one coalesced 256-byte row) and keeps them in registers beside the
-// state; each week it forms the observation the env last produced from its inventory and
-// backlog registers, the L int64 dot products, the shift and the clamp (scg_bg_policy.h). No
-// action rows are requested, so the weeks are not grouped. Every output is optional: with
-// none, and the ring in LDS, a FIXED, POISSON or UNIFORM week touches no HBM (history rows
-// excepted). The sum of the launch's rewards is one int64 per lane.
-struct PolicyArgs {
+// The closed loop: the action rows are computed, by one of the three policies below, so no rows
+// are requested and the weeks are not grouped. Every output is optional: with none, and the ring
+// in LDS, a FIXED, POISSON or UNIFORM week touches no HBM (history rows excepted). The sum of the
+// launch's rewards is one int64 per lane: the `first` launch of a call stores reward_sum, later
+// ones add to it. A source derives from ClosedOut, names in Regs<L> what a lane keeps in registers
+// for the launch, and has a closed_load and (the integer policies) a closed_act<L> overload. The
+// bytes of these kernel arguments are the ones from before the sources shared ClosedOut and
+// LocalStart (hence `first` behind each source's own fields) and Regs<L> is a plain array: the
+// kernels follow either (profiles/r19a_bg_closed_consolidation_isa.txt).
+template <class Param>
+struct ClosedOut {
   static constexpr bool kPolicy = true;
   static constexpr bool kLocal = false;
-  static constexpr bool kMlp = false;
   static constexpr int kGroup = 1;
-  const int32_t* params;  // [L*(L+1)][N]
-  int32_t* acts_out;      // [K][N][L] of this launch, or null
-  int32_t* obs_out;       // [K][N][L] or null
-  int32_t* rew_out;       // [K][N] or null
-  int64_t* reward_sum;    // [N] or null
-  PolicyClamp clamp;
-  int32_t first;          // the first launch of a call stores reward_sum, later ones add to it
+  const Param* params;  // the policy's, in its own layout
+  int32_t* acts_out;    // [K][N][L] of this launch, or null
+  int32_t* obs_out;     // [K][N][L] or null
+  int32_t* rew_out;     // [K][N] or null
+  int64_t* reward_sum;  // [N] or null
 };
 
-// Local: the closed loop with the local-information policy (scg_bg_local.h): 5*L parameter words
-// per lane, and beside the state two more things in registers, the in-transit sum of each level
-// and the last customer demand. Once per launch the lane adds the ring rows the host's mask
-// marks live (bit j-1: the row of week w0 + j, w0 the week the launch starts after) and takes
-// the demand of week w0 (FIXED: from the host; else the draw or table entry of that week; the
-// initial orders value at w0 = 0); each week updates both from registers.
-struct LocalArgs {
-  static constexpr bool kPolicy = true;
-  static constexpr bool kLocal = true;
-  static constexpr bool kMlp = false;
-  static constexpr int kGroup = 1;
-  const int32_t* params;  // [5*L][N]
-  int32_t* acts_out;      // [K][N][L] of this launch, or null
-  int32_t* obs_out;       // [K][N][L] or null
-  int32_t* rew_out;       // [K][N] or null
-  int64_t* reward_sum;    // [N] or null
-  PolicyClamp clamp;
-  int32_t first;          // the first launch of a call stores reward_sum, later ones add to it
-  int32_t last_fixed;     // FIXED demand: customer_demand[w0 - 1] (unused at w0 = 0)
-  uint64_t live;          // local_live_mask of the launch's first state
+// What the sources on the local features (scg_bg_local.h) add, kLocal: a lane also keeps the
+// in-transit sum of each level and the last customer demand in registers. Once per launch it adds
+// the ring rows the host's mask marks live (bit j-1: the row of week w0 + j, w0 the week the launch
+// starts after) and takes the demand of week w0 (FIXED: from the host; else the draw or table entry
+// of that week; the initial orders value at w0 = 0); each week updates both from registers.
+struct LocalStart {
+  int32_t last_fixed;  // FIXED demand: customer_demand[w0 - 1] (unused at w0 = 0)
+  uint64_t live;       // local_live_mask of the launch's first state
 };
 
-// Mlp: the closed loop with the float32 MLP policy on the local features (scg_bg_mlp.h). The
-// in-transit sums and the last demand are LocalArgs's; the parameters are one block shared by
-// every env, read with wave-uniform indices through the scalar cache each week, so no lane keeps
-// parameter registers: beside the state a lane holds the 4L inputs and the L sums. A launch
-// samples when `noise` is non-null (a uniform branch): week k's noise row, L floats per lane laid
-// out like an action row, is requested at the top of the week, before the features exist.
-// samples_out may be the noise buffer: a lane reads its row, then writes it.
-struct MlpArgs {
-  static constexpr bool kPolicy = true;
+// An integer policy's W words of env n (word q of a wave's 64 envs is one coalesced 256-byte row).
+template <int W>
+__device__ __forceinline__ void closed_load(const ClosedOut<int32_t>& src, int64_t N, int64_t n, int32_t (&par)[W]) {
+  param_load(src.params, N, n, par);
+}
+
+// Policy: the per-env linear policy (scg_bg_policy.h), params [L*(L+1)][N]. Each week the lane
+// forms the observation the env last produced from its inventory and backlog registers, the L
+// int64 dot products, the shift and the clamp.
+struct PolicyArgs : ClosedOut<int32_t> {
+  template <int L>
+  using Regs = int32_t[policy_words(L)];
+  PolicyClamp clamp;
+  int32_t first;
+};
+
+// Local: the local-information policy (scg_bg_local.h), params [5*L][N].
+struct LocalArgs : ClosedOut<int32_t> {
   static constexpr bool kLocal = true;
-  static constexpr bool kMlp = true;
-  static constexpr int kGroup = 1;
-  const float* params;    // [Q] (scg_bg_mlp.h), shared
-  int32_t* acts_out;      // [K][N][L] of this launch, or null
-  int32_t* obs_out;       // [K][N][L] or null
-  int32_t* rew_out;       // [K][N] or null
-  int64_t* reward_sum;    // [N] or null
+  template <int L>
+  using Regs = int32_t[local_words(L)];
+  PolicyClamp clamp;
+  int32_t first;
+  LocalStart start;
+};
+
+// Mlp: the float32 MLP policy on the local features (scg_bg_mlp.h). The parameters, [Q], are one
+// block shared by every env, read with wave-uniform indices through the scalar cache each week, so
+// no lane keeps parameter registers: beside the state a lane holds the 4L inputs, the L sums and
+// the L (uniform) standard deviations. A launch samples when `noise` is non-null (a uniform
+// branch): week k's noise row, L floats per lane laid out like an action row, is requested at the
+// top of the week, before the features exist. samples_out may be the noise buffer: a lane reads
+// its row, then writes it. The MLP is still a special case of rollout_body (kMlp there), not behind
+// closed_act, for the time that form cost (profiles/r19a_bg_closed_consolidation_isa.txt).
+struct MlpArgs : ClosedOut<float> {
+  static constexpr bool kLocal = true;
+  template <int L>
+  using Regs = float[L];  // the standard deviations
   const float* std;       // [L]; non-null when noise is
   const float* noise;     // [K][N][L] of this launch, or null: deterministic
   float* samples_out;     // [K][N][L] of this launch (u), or null
   int32_t* features_out;  // [K][N][L][4] of this launch, or null
   int32_t hidden, lo, hi;
-  int32_t first;          // as LocalArgs
-  int32_t last_fixed;
-  uint64_t live;
+  int32_t first;
+  LocalStart start;
 };
+template <int L>
+__device__ __forceinline__ void closed_load(const MlpArgs& src, int64_t, int64_t, float (&sd)[L]) {
+#pragma unroll
+  for (int l = 0; l < L; ++l) sd[l] = src.noise ? const_tab(src.std)[l] : 0.0f;
+}
+static_assert(sizeof(PolicyArgs) == 56 && sizeof(LocalArgs) == 72 && sizeof(MlpArgs) == 104, "the kernel arguments' bytes");
+
+// The week's action of an integer policy, from the observation o the env last produced or (kLocal)
+// the features f of its state.
+template <int L>
+__device__ __forceinline__ void closed_act(const PolicyArgs& src, const int32_t (&par)[policy_words(L)],
+                                           const int32_t (&o)[L], const int32_t (&)[L][kLocalFeatures], int32_t (&act)[L]) {
+  policy_act<L>(par, o, src.clamp, act);
+}
+
+template <int L>
+__device__ __forceinline__ void closed_act(const LocalArgs& src, const int32_t (&par)[local_words(L)],
+                                           const int32_t (&)[L], const int32_t (&f)[L][kLocalFeatures], int32_t (&act)[L]) {
+  local_act<L>(par, f, src.clamp, act);
+}
 
 // The sum of the ring rows `live` marks, from the state after week w0: transit[l] of
 // scg_bg_local.h, in wrapping arithmetic. `live` is uniform, so the loop is scalar.
@@ -1124,17 +1153,11 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
   constexpr int G = Source::kGroup;
   const int64_t row = n * L;
   const int64_t stride = a.n * L;
+  constexpr bool kPolicy = Source::kPolicy;
   constexpr bool kLocal = Source::kLocal;
-  constexpr bool kMlp = Source::kMlp;
-  [[maybe_unused]] int32_t par[kLocal ? L * kLocalRow : L * (L + 1)];
-  [[maybe_unused]] float sd[L];
-  if constexpr (kMlp) {  // shared parameters stay in memory; the L standard deviations are uniform
-#pragma unroll
-    for (int l = 0; l < L; ++l) sd[l] = src.noise ? const_tab(src.std)[l] : 0.0f;
-  } else if constexpr (kLocal)
-    local_load<L>(src.params, a.n, n, par);
-  else if constexpr (Source::kPolicy)
-    policy_load<L>(src.params, a.n, n, par);
+  constexpr bool kMlp = std::is_same_v<Source, MlpArgs>;  // the one source the body knows by name
+  [[maybe_unused]] typename Source::template Regs<L> regs;
+  if constexpr (kPolicy) closed_load(src, a.n, n, regs);
   int32_t inv[L], bk[L], op[L], iacc[L], bacc[L], pacc[L];
   load_row<L>(a.inv + row, inv);
   load_row<L>(a.bk + row, bk);
@@ -1154,12 +1177,12 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
   [[maybe_unused]] int32_t last_demand = 0;
   if constexpr (kLocal) {
     const int32_t w0 = weeks.wk[0].week - 1;
-    local_transit<L>(ring, src.live, w0, a.ring_slots, transit);
-    last_demand = local_last_demand(a, n, w0, src.last_fixed);
+    local_transit<L>(ring, src.start.live, w0, a.ring_slots, transit);
+    last_demand = local_last_demand(a, n, w0, src.start.last_fixed);
   }
   for (int32_t k0 = 0; k0 < K; k0 += G) {
     int32_t group_act[G][L];
-    if constexpr (!Source::kPolicy) {
+    if constexpr (!kPolicy) {
 #pragma unroll
       for (int u = 0; u < G; ++u)
         if (k0 + u < K) load_row<L>(src.acts + (k0 + u) * stride + row, group_act[u]);
@@ -1186,15 +1209,15 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
       }
       int32_t due[L], obs[L], ship[L], cur[L];
       int32_t(&act)[L] = group_act[u];
-      [[maybe_unused]] int32_t eps[L];  // the week's noise row, as bits
+      [[maybe_unused]] int32_t eps[L];  // the MLP's noise row of the week, as bits
       if constexpr (kMlp)
         if (src.noise) load_row<L>(reinterpret_cast<const int32_t*>(src.noise) + k * stride + row, eps);
-      if constexpr (Source::kPolicy) {
+      if constexpr (kPolicy) {
         int32_t o[L];
         policy_obs<L>(inv, bk, kV2 ? a.max_stock : 0, o);
-        if constexpr (kMlp) {
-          int32_t f[L][kLocalFeatures];
-          local_features<L>(o, bk, op, transit, last_demand, f);
+        [[maybe_unused]] int32_t f[L][kLocalFeatures];
+        if constexpr (kLocal) local_features<L>(o, bk, op, transit, last_demand, f);
+        if constexpr (kMlp) {  // see MlpArgs; regs: the L standard deviations
           if (src.features_out) {
 #pragma unroll
             for (int l = 0; l < L; ++l) store_row<kLocalFeatures>(src.features_out + (k * stride + row + l) * kLocalFeatures, f[l]);
@@ -1205,19 +1228,15 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
             int32_t ubits[L];
 #pragma unroll
             for (int l = 0; l < L; ++l) {
-              z[l] = bg_mlp_sample(z[l], sd[l], __int_as_float(eps[l]));
+              z[l] = bg_mlp_sample(z[l], regs[l], __int_as_float(eps[l]));
               ubits[l] = __float_as_int(z[l]);
             }
             if (src.samples_out) store_row<L>(reinterpret_cast<int32_t*>(src.samples_out) + k * stride + row, ubits);
           }
 #pragma unroll
           for (int l = 0; l < L; ++l) act[l] = bg_mlp_finish(z[l], src.lo, src.hi);
-        } else if constexpr (kLocal) {
-          int32_t f[L][kLocalFeatures];
-          local_features<L>(o, bk, op, transit, last_demand, f);
-          local_act<L>(par, f, src.clamp, act);
         } else {
-          policy_act<L>(par, o, src.clamp, act);
+          closed_act<L>(src, regs, o, f, act);
         }
       }
       // the demand draw stands where each variant's kernels have had it, before or after the
@@ -1294,7 +1313,7 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
         ret = 0;
         ++episode;
       }
-      if constexpr (Source::kPolicy)
+      if constexpr (kPolicy)
         if (src.acts_out) store_row<L>(src.acts_out + k * stride + row, act);
       if (src.obs_out) store_row<L>(src.obs_out + k * stride + row, obs);
       if (src.rew_out) src.rew_out[k * a.n + n] = reward;
@@ -1308,7 +1327,7 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
   if constexpr (kV2)
     if (a.pen_acc) store_row<L>(a.pen_acc + row, pacc);
   if (a.ep_ret) a.ep_ret[n] = ret;
-  if constexpr (Source::kPolicy)
+  if constexpr (kPolicy)
     if (src.reward_sum) src.reward_sum[n] = src.first ? sum : src.reward_sum[n] + sum;
   note_overflow(a.err, ovf);
 }
@@ -1345,22 +1364,16 @@ __global__ __launch_bounds__(kBlock) void bg_rollout_kernel(const BgArgs a, int3
   }
 }
 
-// The policy rollout at L levels (1..SCG_BG_POLICY_MAX_LEVELS); defined in scg_bg_policy.hip, the
-// unit that instantiates the closed-loop kernels.
-int bg_launch_policy_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
-                             const RolloutWeeks& weeks, const PolicyArgs& pa);
+// A closed-loop source's rollout at L levels (1..SCG_BG_POLICY_MAX_LEVELS): defined in
+// scg_bg_closed_launch.h, instantiated in scg_bg_policy.hip, scg_bg_local.hip and scg_bg_mlp.hip.
+template <class Source>
+int bg_launch_closed(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, const RolloutWeeks& weeks,
+                     const Source& src);
 
-// The same for the local-information policy, and the features of the state as it stands
-// (out [N][L][4]; w0 = st->week, `live` its mask, last_fixed as in LocalArgs); both defined in
-// scg_bg_local.hip.
-int bg_launch_local_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
-                            const RolloutWeeks& weeks, const LocalArgs& la);
+// The local features of the state as it stands (out [N][L][4]; w0 = st->week, `live` its mask,
+// last_fixed as in LocalStart); defined in scg_bg_local.hip.
 int bg_launch_local_features(dim3 grid, hipStream_t s, const BgArgs& a, int32_t L, int32_t w0, uint64_t live,
                              int32_t last_fixed, int32_t* out);
-
-// The same for the float32 MLP policy; defined in scg_bg_mlp.hip.
-int bg_launch_mlp_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
-                          const RolloutWeeks& weeks, const MlpArgs& ma);
 
 // hipModuleLaunchKernel with the kernel's function handle resolved once per instantiation,
 // skipping the host-stub lookup of hipLaunchKernel on every step: ≈0.5 µs less host time

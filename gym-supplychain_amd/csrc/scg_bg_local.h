@@ -51,16 +51,13 @@ SCG_POLICY_HD int64_t local_param_index(int64_t N, int64_t n, int l, int j) {
 }
 
 SCG_POLICY_HD bool local_valid(int32_t kind, int32_t shift, int32_t lo, int32_t hi) {
-  return kind == SCG_BG_POLICY_LOCAL && shift >= 0 && shift <= kPolicyMaxShift && lo <= hi;
+  return kind == SCG_BG_POLICY_LOCAL && clamp_valid(shift, lo, hi);
 }
 
 // Env n's 5*L words out of the [5*L][N] block.
 template <int L>
 SCG_POLICY_HD void local_load(const int32_t* params, int64_t N, int64_t n, int32_t (&p)[L * kLocalRow]) {
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-  for (int q = 0; q < L * kLocalRow; ++q) p[q] = params[static_cast<int64_t>(q) * N + n];
+  param_load(params, N, n, p);
 }
 
 SCG_POLICY_HD int32_t local_wrap_add(int32_t x, int32_t y) {

@@ -1,8 +1,7 @@
 // The closed-loop BeerGame rollout kernels with the local-information policy
-// (scg_beergame_kernels.h: bg_rollout_kernel with LocalArgs as its source) instantiated for
-// levels 1-8 behind their launcher, and the kernel that writes the policy's features of the
-// state as it stands: a unit of its own, compiled beside the per-level units.
-#include "scg_beergame_kernels.h"
+// (bg_rollout_kernel with LocalArgs as its source), and the kernel that writes the policy's
+// features of the state as it stands: a unit of its own, compiled beside the per-level units.
+#include "scg_bg_closed_launch.h"
 
 namespace scg {
 
@@ -37,15 +36,7 @@ int bg_launch_local_features(dim3 grid, hipStream_t s, const BgArgs& a, int32_t 
   return check_launch("bg_local_features_kernel");
 }
 
-int bg_launch_local_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
-                            const RolloutWeeks& weeks, const LocalArgs& la) {
-  switch (L) {
-#define X(l) \
-  case l: return bg_launch_rollout<l>(variant, grid, s, a, K, weeks, la);
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#undef X
-    default: return fail(SCG_ERR_INVALID, "local policy rollout: levels=%d outside 1..%d", L, SCG_BG_POLICY_MAX_LEVELS);
-  }
-}
+template int bg_launch_closed<LocalArgs>(int, int, dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&,
+                                         const LocalArgs&);
 
 }  // namespace scg

@@ -39,17 +39,28 @@ struct PolicyClamp {
   int32_t shift, lo, hi;
 };
 
+// The shift and the clamp every integer policy takes (scg_bg_local.h too).
+SCG_POLICY_HD bool clamp_valid(int32_t shift, int32_t lo, int32_t hi) {
+  return shift >= 0 && shift <= kPolicyMaxShift && lo <= hi;
+}
+
 SCG_POLICY_HD bool policy_valid(int32_t kind, int32_t shift, int32_t lo, int32_t hi) {
-  return kind == SCG_BG_POLICY_LINEAR && shift >= 0 && shift <= kPolicyMaxShift && lo <= hi;
+  return kind == SCG_BG_POLICY_LINEAR && clamp_valid(shift, lo, hi);
+}
+
+// Env n's W words out of a [W][N] block of per-env parameters.
+template <int W>
+SCG_POLICY_HD void param_load(const int32_t* params, int64_t N, int64_t n, int32_t (&p)[W]) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int q = 0; q < W; ++q) p[q] = params[static_cast<int64_t>(q) * N + n];
 }
 
 // Env n's L*(L+1) words out of the [L*(L+1)][N] block.
 template <int L>
 SCG_POLICY_HD void policy_load(const int32_t* params, int64_t N, int64_t n, int32_t (&p)[L * (L + 1)]) {
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-  for (int q = 0; q < L * (L + 1); ++q) p[q] = params[static_cast<int64_t>(q) * N + n];
+  param_load(params, N, n, p);
 }
 
 // One level's action from its row of words (L weights, then the bias). A product of two int32

@@ -1,19 +1,10 @@
-// The closed-loop BeerGame rollout kernels (scg_beergame_kernels.h: bg_rollout_kernel with
-// PolicyArgs as its source) instantiated for levels 1-8 behind their launcher: a unit of its
-// own, compiled beside the per-level units.
-#include "scg_beergame_kernels.h"
+// The closed-loop BeerGame rollout kernels with the per-env linear policy (bg_rollout_kernel with
+// PolicyArgs as its source): a unit of its own, compiled beside the per-level units.
+#include "scg_bg_closed_launch.h"
 
 namespace scg {
 
-int bg_launch_policy_rollout(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K,
-                             const RolloutWeeks& weeks, const PolicyArgs& pa) {
-  switch (L) {
-#define X(l) \
-  case l: return bg_launch_rollout<l>(variant, grid, s, a, K, weeks, pa);
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#undef X
-    default: return fail(SCG_ERR_INVALID, "policy rollout: levels=%d outside 1..%d", L, SCG_BG_POLICY_MAX_LEVELS);
-  }
-}
+template int bg_launch_closed<PolicyArgs>(int, int, dim3, hipStream_t, const BgArgs&, int32_t, const RolloutWeeks&,
+                                          const PolicyArgs&);
 
 }  // namespace scg

@@ -103,31 +103,48 @@ class BeerGameConfig:
         self.initial_orders_value = _int32("initial_orders_value", info.get("initial_orders_value", STD_ORDERS_VALUE))
 
 
-class PackedPolicy:
+class _Packed:
+    """Policy parameters on the env's device, packed for n_envs envs of `levels` levels. A subclass
+    names its policy struct, kind and entry point."""
+    __slots__ = ("params", "n_envs", "levels")
+
+    def __init__(self, params, n_envs, levels):
+        self.params, self.n_envs, self.levels = params, n_envs, levels
+
+    def _policy(self, shift, lo, hi):
+        """The ctypes policy struct of a call: an integer policy's shift and clamp."""
+        return self._struct(kind=self._kind, shift=shift, act_lo=lo, act_hi=hi, params=self.params.data_ptr())
+
+
+class PackedPolicy(_Packed):
     """Per-env linear policy parameters as scg_bg_rollout_policy reads them
     (BeerGameVecEnv.pack_policy): `params` int32 [L*(L+1), N] on the env's device."""
-    __slots__ = ("params", "n_envs", "levels")
-
-    def __init__(self, params, n_envs, levels):
-        self.params, self.n_envs, self.levels = params, n_envs, levels
+    __slots__ = ()
+    _struct, _kind, _entry = nat.BgPolicy, nat.BG_POLICY_LINEAR, "scg_bg_rollout_policy"
 
 
-class PackedLocalPolicy:
+class PackedLocalPolicy(_Packed):
     """Per-env local-information policy parameters as scg_bg_rollout_local reads them
     (BeerGameVecEnv.pack_local_policy): `params` int32 [5*L, N] on the env's device."""
-    __slots__ = ("params", "n_envs", "levels")
-
-    def __init__(self, params, n_envs, levels):
-        self.params, self.n_envs, self.levels = params, n_envs, levels
+    __slots__ = ()
+    _struct, _kind, _entry = nat.BgLocalPolicy, nat.BG_POLICY_LOCAL, "scg_bg_rollout_local"
 
 
-class PackedLocalMlp:
+class PackedLocalMlp(_Packed):
     """One shared float32 MLP policy over the local features as scg_bg_rollout_mlp reads it
     (BeerGameVecEnv.pack_local_mlp): `params` float32 [Q] on the env's device."""
-    __slots__ = ("params", "n_envs", "levels", "hidden")
+    __slots__ = ("hidden",)
+    _struct, _kind, _entry = nat.BgMlp, nat.BG_POLICY_MLP, "scg_bg_rollout_mlp"
 
     def __init__(self, params, n_envs, levels, hidden):
-        self.params, self.n_envs, self.levels, self.hidden = params, n_envs, levels, hidden
+        super().__init__(params, n_envs, levels)
+        self.hidden = hidden
+
+    def _policy(self, lo, hi, std, noise, samples_out, features_out):
+        """The ctypes policy struct of a call: the clamp and the optional buffers (tensors or None)."""
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        return self._struct(kind=self._kind, hidden=self.hidden, act_lo=lo, act_hi=hi, params=self.params.data_ptr(),
+                            std=ptr(std), noise=ptr(noise), samples_out=ptr(samples_out), features_out=ptr(features_out))
 
 
 class PolicyRollout:
@@ -507,15 +524,19 @@ class BeerGameVecEnv:
             x = y
         return x
 
+    def _policy_shape(self):
+        """(N, L) of a policy packed for this env; ValueError past the closed loop's level limit."""
+        if self.levels > nat.BG_POLICY_MAX_LEVELS:
+            raise ValueError(f"rollout_policy supports up to {nat.BG_POLICY_MAX_LEVELS} levels, this env has {self.levels}")
+        return self.n_envs, self.levels
+
     def pack_policy(self, weights, bias):
         """Per-env linear policy parameters in the layout scg_bg_rollout_policy reads: int32
         [L*(L+1), N] on this env's device, word l*(L+1)+j of an env being weights[l][j] for
         j < L and bias[l] for j == L. weights is [N, L, L] or [L, L], bias [N, L] or [L]
         (shared forms are broadcast). Pass the result to rollout_policy() to pack once for
         many calls."""
-        N, L = self.n_envs, self.levels
-        if L > nat.BG_POLICY_MAX_LEVELS:
-            raise ValueError(f"rollout_policy supports up to {nat.BG_POLICY_MAX_LEVELS} levels, this env has {L}")
+        N, L = self._policy_shape()
         w = self._exact_int32("weights", weights, ((N, L, L), (L, L))).expand(N, L, L)
         b = self._exact_int32("bias", bias, ((N, L), (L,))).expand(N, L)
         words = torch.cat([w, b.unsqueeze(2)], dim=2).reshape(N, L * (L + 1))
@@ -573,7 +594,7 @@ class BeerGameVecEnv:
         [K, N, L, 4] features each week's action was computed from. The result's `samples` and
         `features` carry them. With an integer policy these four arguments raise ValueError."""
         N, L = self.n_envs, self.levels
-        if isinstance(weights, (PackedPolicy, PackedLocalPolicy, PackedLocalMlp)):
+        if isinstance(weights, _Packed):
             if bias is not None:
                 raise ValueError("a packed policy carries its bias")
             packed = weights
@@ -613,15 +634,10 @@ class BeerGameVecEnv:
             res.samples = samples_out
             res.features = torch.empty((K, N, L, nat.BG_LOCAL_FEATURES), **i32) if return_features else None
             bufs = (sd, noise, samples_out, res.features) if K else (None,) * 4  # no weeks: empty tensors, no pointers
-            pol = nat.BgMlp(nat.BG_POLICY_MLP, packed.hidden, lo, hi, packed.params.data_ptr(),
-                            *(None if t is None else t.data_ptr() for t in bufs))
-            entry = nat.lib.scg_bg_rollout_mlp
-        elif isinstance(packed, PackedLocalPolicy):
-            pol = nat.BgLocalPolicy(nat.BG_POLICY_LOCAL, int(shift), lo, hi, packed.params.data_ptr())
-            entry = nat.lib.scg_bg_rollout_local
+            pol = packed._policy(lo, hi, *bufs)
         else:
-            pol = nat.BgPolicy(nat.BG_POLICY_LINEAR, int(shift), lo, hi, packed.params.data_ptr())
-            entry = nat.lib.scg_bg_rollout_policy
+            pol = packed._policy(int(shift), lo, hi)
+        entry = getattr(nat.lib, packed._entry)
         nat.check(entry(self._cfg_ref, self._st_ref, int(n_weeks), ctypes.byref(pol), nat.ptr(res.actions),
                         nat.ptr(res.obs), nat.ptr(res.rewards), res.reward_sum.data_ptr(), self._flags, self._stream()))
         return res
@@ -632,9 +648,7 @@ class BeerGameVecEnv:
         (net, line, down, own: see rollout_policy) and bias[l] for j == 4. weights is [N, L, 4]
         or [L, 4], bias [N, L] or [L] (shared forms are broadcast); values must be exact int32.
         Pass the result to rollout_policy(packed, None, n_weeks, ...)."""
-        N, L, F = self.n_envs, self.levels, nat.BG_LOCAL_FEATURES
-        if L > nat.BG_POLICY_MAX_LEVELS:
-            raise ValueError(f"rollout_policy supports up to {nat.BG_POLICY_MAX_LEVELS} levels, this env has {L}")
+        (N, L), F = self._policy_shape(), nat.BG_LOCAL_FEATURES
         w = self._exact_int32("weights", weights, ((N, L, F), (L, F))).expand(N, L, F)
         b = self._exact_int32("bias", bias, ((N, L), (L,))).expand(N, L)
         words = torch.cat([w, b.unsqueeze(2)], dim=2).reshape(N, L * (F + 1))
@@ -652,9 +666,7 @@ class BeerGameVecEnv:
         representable as float32. ValueError otherwise, and for per-env shapes ([N, ...]): the
         network is shared; populations of per-env parameters are what pack_local_policy() serves.
         Pass the result to rollout_policy(packed, None, n_weeks, ...)."""
-        N, L = self.n_envs, self.levels
-        if L > nat.BG_POLICY_MAX_LEVELS:
-            raise ValueError(f"rollout_policy supports up to {nat.BG_POLICY_MAX_LEVELS} levels, this env has {L}")
+        N, L = self._policy_shape()
         I = L * nat.BG_LOCAL_FEATURES
         shape = tuple(w1.shape) if hasattr(w1, "shape") else tuple(np.shape(w1))
         if len(shape) == 3:

@@ -11,9 +11,13 @@ sample being the wall clock of `--episodes` calls of 35 weeks between two device
   rollout1         BeerGameVecEnv.rollout, Poisson demand, a delay list;
   rollout2         BeerGame2VecEnv.rollout, demand (0, 16), delays (0, 5);
   rollout_policy1  rollout_policy on the first env, no output but reward_sum;
-  rollout_policy2  rollout_policy on the second.
+  rollout_policy2  rollout_policy on the second;
+  rollout_local1, rollout_local2            the same with a pack_local_policy() policy;
+  rollout_mlp_det2, rollout_mlp_sampled2    the second env with a pack_local_mlp() policy of H = 16,
+                   deterministic, and sampled with noise= and samples_out= preallocated.
 The policy draw is that of tools/bg_policy_rollout_ab.py: per-env weights in [-64, 64], biases in
-[-2000, 2000], shift 4; BeerGameVecEnv's order increments are clamped to (-3, 7). A process
+[-2000, 2000], shift 4; BeerGameVecEnv's order increments are clamped to (-3, 7). The MLP draw is
+that of tools/bg_mlp_rollout_ab.py. A process
 reports the median of its three samples per path, in microseconds per week of the batch. The
 summary gives, per path and build, the median, minimum and maximum of the rounds' figures, and
 whether this tree's median lies inside the other build's minimum .. maximum, else by how much
@@ -28,8 +32,10 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PATHS = ("rollout1", "rollout2", "rollout_policy1", "rollout_policy2")
-LEVELS, WEEKS, SEED, SHIFT = 4, 35, 0x5EED0000, 4
+PATHS = ("rollout1", "rollout2", "rollout_policy1", "rollout_policy2", "rollout_local1", "rollout_local2",
+         "rollout_mlp_det2", "rollout_mlp_sampled2")
+LEVELS, WEEKS, SEED, SHIFT, HIDDEN = 4, 35, 0x5EED0000, 4, 16
+CHILD_TIMEOUT = 900  # the four first paths fit 300 s; an MLP week costs about three linear ones
 DELAYS = [2, 0, 3, 1, 1, 4, 2] * 5
 CLIP1 = (-3, 7)  # BeerGameEnv's actions are increments over the incoming order
 
@@ -53,17 +59,29 @@ def child(a):
     gen = torch.Generator(device="cpu").manual_seed(SEED)
     W = torch.randint(-64, 65, (N, L, L), generator=gen, dtype=torch.int32).to(dev)
     b = torch.randint(-2000, 2001, (N, L), generator=gen, dtype=torch.int32).to(dev)
-    packed = envs["rollout_policy1"].pack_policy(W, b)
+    packed = {"policy": envs["rollout_policy1"].pack_policy(W, b)}
     acts = {"rollout1": torch.randint(-3, 8, (T, N, L), generator=gen, dtype=torch.int32).to(dev),
             "rollout2": torch.randint(0, 16, (T, N, L), generator=gen, dtype=torch.int32).to(dev)}
     obs = torch.empty((T, N, L), dtype=torch.int32, device=dev)
     rew = torch.empty((T, N), dtype=torch.int32, device=dev)
+    W4 = torch.randint(-64, 65, (N, L, 4), generator=gen, dtype=torch.int32).to(dev)
+    packed["local"] = envs["rollout_local1"].pack_local_policy(W4, b)
+    gen = torch.Generator(device="cpu").manual_seed(SEED)
+    rnd = lambda *shape: torch.randn(*shape, generator=gen, dtype=torch.float32)  # noqa: E731
+    H = HIDDEN
+    w1, b1, w2, b2 = rnd(H, 4 * L) / 40, rnd(H), 2 * rnd(L, H) / H ** 0.5, 8 + rnd(L)
+    std, noise = (2 * torch.exp(0.3 * rnd(L))).to(dev), rnd(T, N, L).to(dev)
+    mlp = envs["rollout_mlp_det2"].pack_local_mlp(*(x.to(dev) for x in (w1, b1, w2, b2)))
+    sampled = dict(noise=noise, std=std, samples_out=torch.empty_like(noise))
 
     def run(name):
         if name in acts:
             envs[name].rollout(acts[name], obs, rew)
+        elif "mlp" in name:
+            envs[name].rollout_policy(mlp, None, T, **(sampled if "sampled" in name else {}))
         else:
-            envs[name].rollout_policy(packed, None, T, shift=SHIFT, clip=CLIP1 if name.endswith("1") else None)
+            envs[name].rollout_policy(packed[name[len("rollout_"):-1]], None, T, shift=SHIFT,
+                                      clip=CLIP1 if name.endswith("1") else None)
 
     def sample(name):
         torch.cuda.synchronize(dev)
@@ -101,7 +119,8 @@ def main():
     got = {name: {k: [] for k in PATHS} for name, _ in builds}
     for r in range(a.rounds):
         for name, root in builds:
-            p = subprocess.run(cmd, env=dict(os.environ, SCG_PKG_ROOT=root), capture_output=True, text=True, timeout=300)
+            p = subprocess.run(cmd, env=dict(os.environ, SCG_PKG_ROOT=root), capture_output=True, text=True,
+                               timeout=CHILD_TIMEOUT)
             if p.returncode != 0:  # a process that failed ends the run: nothing more is started
                 raise SystemExit(f"round {r + 1} {name}: exit status {p.returncode}\n{p.stderr[-2000:]}")
             res = json.loads(p.stdout.strip().splitlines()[-1])
