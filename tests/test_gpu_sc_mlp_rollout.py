@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from sc_closed_ref import clamp, policy_z
 from test_gpu_sc_policy_rollout import LO, HI, _bits, _sequential_sum, small_launches  # noqa: F401 (autouse fixture)
 from test_gpu_sc_rollout import DEV, STOCH, _actions, _pair, _same_state
 
@@ -33,24 +34,11 @@ def _params(env, hidden, shared=False, seed=3):
     return w1, b1, w2, b2
 
 
-def _layer(x, w, b):
-    """z [N, R] = b, then + w[:, :, j] * x[:, j] in ascending j, each product and sum rounded to float32."""
-    n = x.shape[0]
-    w = np.broadcast_to(w, (n,) + w.shape[-2:])
-    z = np.broadcast_to(b, (n, w.shape[1])).astype(np.float32).copy()
-    with np.errstate(all="ignore"):
-        for j in range(x.shape[1]):
-            z = (z + (w[:, :, j] * x[:, None, j]).astype(np.float32)).astype(np.float32)
-    return z
-
-
 def _formula(obs, params, lo=LO, hi=HI):
-    """The policy as scgpu.h states it, in NumPy float32: obs [N, O] -> (hidden [N, H], actions [N, A])."""
-    w1, b1, w2, b2 = params
-    pre = _layer(obs.astype(np.float32), w1, b1)
-    hid = np.where(pre > 0, pre, np.float32(0.0)).astype(np.float32)
-    z = _layer(hid, w2, b2)
-    return hid, np.where(~(z >= lo), lo, np.where(z > hi, hi, z)).astype(np.float32)
+    """The policy as scgpu.h states it, in NumPy float32 (tests/sc_closed_ref.py): obs [N, O] ->
+    (hidden [N, H], actions [N, A])."""
+    hid, z = policy_z(obs, params)
+    return hid, clamp(z, lo, hi)
 
 
 def _closed_loop_is_open_loop(env, twin, packed, params, k, what=""):

@@ -13,10 +13,10 @@ import numpy as np
 import pytest
 import torch
 
+from sc_closed_ref import HI, LO, clamp, layer
 from test_gpu_sc_rollout import DEV, STOCH, _actions, _pair, _same_state
 
 pytestmark = pytest.mark.gpu
-LO, HI = np.float32(-1.0), np.float32(1.0)
 
 
 @pytest.fixture(autouse=True)
@@ -43,16 +43,8 @@ def _params(env, shared=False, seed=3, n=None):
 
 
 def _formula(obs, w, b, lo=LO, hi=HI):
-    """The policy as scgpu.h states it, in NumPy float32: obs [N, O] -> actions [N, A]."""
-    o = obs.astype(np.float32)
-    n = o.shape[0]
-    w = np.broadcast_to(w, (n,) + w.shape[-2:])
-    z = np.broadcast_to(b, (n, w.shape[1])).astype(np.float32).copy()
-    with np.errstate(all="ignore"):
-        for j in range(o.shape[1]):
-            term = (w[:, :, j] * o[:, None, j]).astype(np.float32)
-            z = (z + term).astype(np.float32)
-        return np.where(~(z >= lo), lo, np.where(z > hi, hi, z)).astype(np.float32)
+    """The policy as scgpu.h states it, in NumPy float32 (tests/sc_closed_ref.py): obs [N, O] -> actions [N, A]."""
+    return clamp(layer(obs.astype(np.float32), w, b), lo, hi)
 
 
 def _bits(x):

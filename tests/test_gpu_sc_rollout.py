@@ -65,6 +65,7 @@ def _roll_equals_steps(rolled, stepped, acts, what=""):
     _same_state(rolled, stepped, what)
     assert torch.equal(rolled._term_obs, stepped._term_obs), what
     rolled.check_errors()
+    return obs, rew, dones
 
 
 @pytest.mark.parametrize("obs_dtype", [torch.float64, torch.float32])

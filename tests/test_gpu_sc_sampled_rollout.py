@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_sc_mlp_rollout import _layer
+from sc_closed_ref import policy_z
+from sc_closed_ref import sample as _sample
 from test_gpu_sc_mlp_rollout import _params as _mlp_params
 from test_gpu_sc_policy_rollout import LO, HI, _bits, _sequential_sum, small_launches  # noqa: F401 (autouse fixture)
 from test_gpu_sc_policy_rollout import _params as _linear_params
@@ -38,19 +39,7 @@ def _noise(env, k, seed=17):
 
 def _z(obs, params):
     """The policy's output before its clamp, in NumPy float32: linear (w, b) or MLP (w1, b1, w2, b2)."""
-    x = obs.astype(np.float32)
-    if len(params) == 2:
-        return _layer(x, *params)
-    w1, b1, w2, b2 = params
-    pre = _layer(x, w1, b1)
-    return _layer(np.where(pre > 0, pre, np.float32(0.0)).astype(np.float32), w2, b2)
-
-
-def _sample(z, std, eps, lo=LO, hi=HI):
-    """(u, action) of the sampled formula: the product rounded to float32, then the sum, then the clamp."""
-    with np.errstate(all="ignore"):
-        u = (z + (std[None, :] * eps).astype(np.float32)).astype(np.float32)
-    return u, np.where(~(u >= lo), lo, np.where(u > hi, hi, u)).astype(np.float32)
+    return policy_z(obs, params)[1]
 
 
 def _dev(x):
