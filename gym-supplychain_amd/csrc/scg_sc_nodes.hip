@@ -214,6 +214,14 @@ struct NodesNoise {
   const float* eps;  // the env's noise row [A]
   float* out;        // the env's row of samples_out [A], or null
 };
+// A drawn launch (ScDrawnLaunch, kDrawn): the env's noise row is not in memory but computed,
+// element (row, env, q) of the launch's key (csrc/scg_normal.h).
+struct NodesDrawn {
+  const float* std;  // [A]
+  float* out;        // the env's row of samples_out [A], or null
+  uint32_t k0, k1, row, env;
+  __device__ __forceinline__ float eps(int q) const { return sc_noise_element(k0, k1, row, env, static_cast<uint32_t>(q)); }
+};
 template <class Launch>
 struct NodesClosedStep {
   static constexpr bool kKeepsState = true;
@@ -222,6 +230,7 @@ struct NodesClosedStep {
   static constexpr bool kPolicy = true;
   static constexpr bool kMlp = Launch::kMlp;
   static constexpr bool kSampled = Launch::kSampled;
+  static constexpr bool kDrawn = Launch::kDrawn;
   const Launch& p;
   int32_t t_, flags_;
   uint32_t episode_;
@@ -246,10 +255,17 @@ struct NodesClosedStep {
   __device__ __forceinline__ bool write_back() const { return write_back_; }
   __device__ __forceinline__ bool first() const { return k_ == 0; }
   __device__ __forceinline__ bool last() const { return last_; }
-  __device__ __forceinline__ NodesNoise noise(const ScArgs& x, int64_t n, int row) const {
+  __device__ __forceinline__ auto noise(const ScArgs& x, int64_t n, int row) const {
     const int64_t at = sc_sample_index(x.n, x.c.A, row, n, 0);
-    return NodesNoise{p.smp.std, p.smp.noise + at, p.smp.samples ? p.smp.samples + at : nullptr};
+    if constexpr (kDrawn) {
+      return NodesDrawn{p.drw.std, p.drw.samples ? p.drw.samples + at : nullptr, p.drw.k0, p.drw.k1,
+                        p.drw.row0 + static_cast<uint32_t>(row), p.drw.env0 + static_cast<uint32_t>(n)};
+    } else {
+      return NodesNoise{p.smp.std, p.smp.noise + at, p.smp.samples ? p.smp.samples + at : nullptr};
+    }
   }
+  // what noise() returns: what a step's act holds between its request and its actions
+  using Noise = std::conditional_t<kDrawn, NodesDrawn, NodesNoise>;
 };
 
 // The closed loop's product: wave w computes actions w, w + W, ... of its lane's env (n) from
@@ -274,6 +290,13 @@ __device__ __forceinline__ void sc_nodes_noise_request(const NodesNoise& nz, int
 #pragma unroll
   for (int u = 0; u < kNodesNoiseAhead; ++u) ev[u] = w + u * W < A ? nz.eps[w + u * W] : 0.0f;
 }
+// The drawn step's: no load; the same elements are computed here, ahead of the first parameter
+// words, which they do not depend on (one Philox block and one pair per element: a block's other
+// pair belongs to another wave's thread, and sharing it would cost LDS and a barrier).
+__device__ __forceinline__ void sc_nodes_noise_request(const NodesDrawn& nz, int A, int w, int W, float (&ev)[kNodesNoiseAhead]) {
+#pragma unroll
+  for (int u = 0; u < kNodesNoiseAhead; ++u) ev[u] = w + u * W < A ? nz.eps(w + u * W) : 0.0f;
+}
 
 // Actions w, w + W, ... of the lane's env into its row of the action tile, each the finish
 // (scg_sc_policy.h) of z(q), the policy's value of action q before its clamp: the clamp to
@@ -297,6 +320,22 @@ __device__ __forceinline__ void sc_nodes_actions(const View& pv, int A, int w, i
     for (int q = w; q < A; q += W) arow[q] = sc_policy_clamp(z(q), pv.lo, pv.hi);
   }
 }
+// The drawn step's (always sampled): elements past those computed ahead are drawn as it comes to them.
+template <bool kSampled, class View, class Z>
+__device__ __forceinline__ void sc_nodes_actions(const View& pv, int A, int w, int W, float* arow, const Z& z,
+                                                 const NodesDrawn& nz, const float (&ev)[kNodesNoiseAhead]) {
+  static_assert(kSampled, "a drawn step is a sampled one");
+  auto one = [&](int q, float eps) {
+    const float sd = nz.std[q];
+    float u;
+    arow[q] = sc_policy_clamp_sampled(z(q), sd, eps, pv.lo, pv.hi, &u);
+    if (nz.out) __hip_atomic_store(&nz.out[q], u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+#pragma unroll
+  for (int u = 0; u < kNodesNoiseAhead; ++u)
+    if (w + u * W < A) one(w + u * W, ev[u]);
+  for (int q = w + kNodesNoiseAhead * W; q < A; q += W) one(q, nz.eps(q));
+}
 
 // The linear policy's act, for step sp.k_ + ahead of the launch (its noise row).
 template <class Step, class ObsT>
@@ -306,7 +345,7 @@ __device__ __forceinline__ void sc_nodes_policy_act(const Step& sp, const ScArgs
   const int A = a.c.A, O = a.c.O;
   // the sampled step's alone: a deterministic step sets neither, and sc_nodes_actions<false>
   // reads neither
-  [[maybe_unused]] NodesNoise nz{};
+  [[maybe_unused]] typename Step::Noise nz{};
   [[maybe_unused]] float ev[kNodesNoiseAhead];
   if constexpr (Step::kSampled) {
     nz = sp.noise(a, n, sp.k_ + ahead);
@@ -331,7 +370,7 @@ __device__ __forceinline__ void sc_nodes_mlp_act(const Step& sp, const ScArgs& a
   const int A = a.c.A, O = a.c.O;
   // the sampled step's alone: a deterministic step sets neither, and sc_nodes_actions<false>
   // reads neither
-  [[maybe_unused]] NodesNoise nz{};
+  [[maybe_unused]] typename Step::Noise nz{};
   [[maybe_unused]] float ev[kNodesNoiseAhead];
   if constexpr (Step::kSampled) nz = sp.noise(a, n, sp.k_ + ahead);
   if (live) {
@@ -347,7 +386,7 @@ __device__ __forceinline__ void sc_nodes_mlp_act(const Step& sp, const ScArgs& a
   }
 }
 
-// A closed-loop step's act, whichever of the four its launch is: the actions of every live env
+// A closed-loop step's act, whichever of the six its launch is: the actions of every live env
 // of the tile for step sp.k_ + ahead of the launch (ahead 0: this step's own, at the launch's
 // first step; 1: the next step's), from the observation tile (orow: the lane's row) into the
 // action tile act_t; `idle` is the LDS the MLP's hidden tile lies over. Every thread of the block
@@ -809,20 +848,20 @@ void sc_rollout_nodes_kernel(const ScArgs a_arg, int W, int E, int K, int obs_mo
 }
 
 // ---- closed-loop rollout: the rollout kernel with the action tile computed on chip --------
-// (scg_sc_rollout_policy, scg_sc_rollout_mlp, scg_sc_rollout_sampled; csrc/scg_sc_policy.h,
-// csrc/scg_sc_mlp.h.) The rollout kernel's block, LDS layout, persistent tile loop and step loop
+// (scg_sc_rollout_policy, scg_sc_rollout_mlp, scg_sc_rollout_sampled, scg_sc_rollout_drawn;
+// csrc/scg_sc_policy.h, csrc/scg_sc_mlp.h, csrc/scg_normal.h.) The rollout kernel's block, LDS layout, persistent tile loop and step loop
 // under NodesClosedStep<Launch>: a tile's first step in the launch loads its envs' last
 // observation rows (obs_io) into the observation tile and computes the first action tile from
 // it; after every other step each wave computes its share of the next action tile from the
 // observation tile the step just completed, so between two kept steps nothing crosses HBM but
 // the policy's parameter words (and the outputs asked for, and a sampled launch's noise). The
 // launch's last step leaves obs_io, act_work, reward_sum and the state in HBM.
-// One kernel template, four instantiations per (MAXD, F64), one per launch type: the linear
-// policy or the one-hidden-layer policy, deterministic (ScClosedLaunch) or sampled
-// (ScSampledLaunch). Where the linear step computes its action tile, every wave of an MLP step
+// One kernel template, six instantiations per (MAXD, F64), one per launch type: the linear
+// policy or the one-hidden-layer policy, deterministic (ScClosedLaunch), sampled from the caller's
+// noise (ScSampledLaunch) or from noise computed here (ScDrawnLaunch, scg_sc_rollout_drawn). Where the linear step computes its action tile, every wave of an MLP step
 // first computes its share of the hidden units into a tile over LDS the step leaves idle there
 // (sc_nodes_mlp_act; the note at the end of sc_nodes_tile), so the block's LDS is the same for
-// all four; what a launch type does not use (the hidden stage, the noise) is not in its code.
+// all six; what a launch type does not use (the hidden stage, the noise) is not in its code.
 // The step loop is this kernel's body and, once more, the open-loop rollout kernel's: as the
 // body of a kernel template it compiles for every launch type to the code of a kernel written
 // out for that type alone (instruction counts, registers and scratch compared per
@@ -1171,6 +1210,8 @@ int sc_launch_nodes_closed_d(const ScArgs& a, const Launch& p, int W, int E, int
   if (cap > 0 && cap < blocks) blocks = cap;
   hipLaunchKernelGGL(kKernel, dim3(static_cast<unsigned>(blocks)), dim3(64 * W), lds, s, ScClosedKArgs<Launch>{a, p}, W, E, K);
   // the error says which policy, and whether sampled
+  if constexpr (Launch::kDrawn)
+    return check_launch(Launch::kMlp ? "sc_closed_rollout_nodes_kernel (mlp, drawn)" : "sc_closed_rollout_nodes_kernel (linear, drawn)");
   return check_launch(Launch::kMlp ? (Launch::kSampled ? "sc_closed_rollout_nodes_kernel (mlp, sampled)"
                                                        : "sc_closed_rollout_nodes_kernel (mlp)")
                                    : (Launch::kSampled ? "sc_closed_rollout_nodes_kernel (linear, sampled)"
@@ -1181,8 +1222,11 @@ int sc_launch_nodes_closed_d(const ScArgs& a, const Launch& p, int W, int E, int
 // block's LDS (sc_nodes_tile): a wider one would run into the stocks behind them.
 template <class Launch>
 int sc_launch_nodes_closed(const ScArgs& a, const Launch& p, int maxd_bucket, int W, int E, int K, hipStream_t s) {
-  if constexpr (Launch::kSampled)
+  if constexpr (Launch::kDrawn) {
+    if (!p.drw.std) return fail(SCG_ERR_INVALID, "drawn closed-loop rollout: std is required");
+  } else if constexpr (Launch::kSampled) {
     if (!p.smp.std || !p.smp.noise) return fail(SCG_ERR_INVALID, "sampled closed-loop rollout: std and noise are required");
+  }
   if constexpr (Launch::kMlp)
     if (p.pv.H < 1 || p.pv.H > sc_mlp_fused_hidden_max(E, a.c.n_nodes))
       return fail(SCG_ERR_INVALID, "closed-loop rollout: %d hidden units do not fit the block's idle LDS", p.pv.H);
@@ -1201,6 +1245,8 @@ template int sc_launch_nodes_closed(const ScArgs&, const ScClosedLaunch<ScPolicy
 template int sc_launch_nodes_closed(const ScArgs&, const ScClosedLaunch<ScMlpView>&, int, int, int, int, hipStream_t);
 template int sc_launch_nodes_closed(const ScArgs&, const ScSampledLaunch<ScPolicyView>&, int, int, int, int, hipStream_t);
 template int sc_launch_nodes_closed(const ScArgs&, const ScSampledLaunch<ScMlpView>&, int, int, int, int, hipStream_t);
+template int sc_launch_nodes_closed(const ScArgs&, const ScDrawnLaunch<ScPolicyView>&, int, int, int, int, hipStream_t);
+template int sc_launch_nodes_closed(const ScArgs&, const ScDrawnLaunch<ScMlpView>&, int, int, int, int, hipStream_t);
 
 // The step server's block for a config the batch kernel runs (float64 observations, no
 // ledgers): one block of W waves with the batch kernel's LDS.

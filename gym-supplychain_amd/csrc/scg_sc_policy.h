@@ -23,7 +23,9 @@
 //   act_a = !(u_a >= lo) ? lo : (u_a > hi ? hi : u_a)
 //
 // k the step's index in the call; a NaN u (a NaN z, 0 * inf) gives lo. sc_policy_sample is the
-// one definition of u.
+// one definition of u. A drawn loop (scg_sc_rollout_drawn, scg_sc_noise_draw) is the sampled one
+// with eps[k][n][a] not read but computed: element (row0 + k, env_offset + n, a) of the seed's
+// noise (csrc/scg_normal.h).
 #pragma once
 
 #include <cstdint>
@@ -112,6 +114,16 @@ struct ScSampleView {
   float* samples;  // or null
 };
 
+// The noise of one launch (or one step's action kernel) of a drawn closed loop: std [A], the
+// rows the samples go to when asked for, the Philox key of the seed, the global row index of the
+// first step and the global id of env 0 (csrc/scg_normal.h: what element (row, env, a) is).
+struct ScDrawView {
+  const float* std;
+  float* samples;  // or null
+  uint32_t k0, k1;
+  uint32_t row0, env0;
+};
+
 // Element (k, n, a) of the noise and sample rows.
 SCG_SC_POLICY_HD int64_t sc_sample_index(int64_t N, int A, int64_t k, int64_t n, int a) { return (k * N + n) * A + a; }
 
@@ -147,6 +159,7 @@ SCG_SC_POLICY_HD float sc_policy_action_sampled(const ScPolicyView& pv, int O, i
 template <class View>
 struct ScClosedLaunch {
   static constexpr bool kSampled = false;
+  static constexpr bool kDrawn = false;
   static constexpr bool kMlp = View::kMlp;
   View pv;
   void* obs_io;         // [N][O], obs dtype: read at the launch's first step, written at its last
@@ -164,5 +177,13 @@ struct ScSampledLaunch : ScClosedLaunch<View> {
 };
 static_assert(sizeof(ScSampledLaunch<ScPolicyView>) == sizeof(ScClosedLaunch<ScPolicyView>) + sizeof(ScSampleView),
               "the kernel arguments: smp directly behind the common fields");
+
+// A drawn closed-loop launch: a sampled one that computes its noise (kDrawn) instead of reading it.
+template <class View>
+struct ScDrawnLaunch : ScClosedLaunch<View> {
+  static constexpr bool kSampled = true;
+  static constexpr bool kDrawn = true;
+  ScDrawView drw;
+};
 
 }  // namespace scg

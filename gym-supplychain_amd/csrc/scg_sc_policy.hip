@@ -1,14 +1,16 @@
 // SupplyChain closed loop, host side and the small kernels (include/scgpu.h scg_sc_observe,
-// scg_sc_rollout_policy, scg_sc_rollout_mlp, scg_sc_rollout_sampled): the observation of a state
+// scg_sc_rollout_policy, scg_sc_rollout_mlp, scg_sc_rollout_sampled, scg_sc_rollout_drawn,
+// scg_sc_noise_fill): the observation of a state
 // as it stands, the action rows of a linear policy or a one-hidden-layer ReLU policy from
-// observation rows, deterministic or with the caller's noise added before the clamp
-// (csrc/scg_sc_policy.h, csrc/scg_sc_mlp.h: the one definition of each formula), and the entry
+// observation rows, deterministic or with noise added before the clamp, the caller's or drawn here
+// (csrc/scg_sc_policy.h, csrc/scg_sc_mlp.h, csrc/scg_normal.h: the one definition of each formula), and the entry
 // points, one host body for both policies, which runs either the fused kernel (scg_sc_nodes.hip
 // sc_closed_rollout_nodes_kernel) or, for every other case, the action kernel and scg_sc_step
 // per step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "scg_common.h"
 #include "scg_supplychain_core.h"
@@ -50,17 +52,26 @@ __device__ __forceinline__ auto sc_with_obs_row(const void* obs, int obs_f64, in
 // kSampled (scg_sc_rollout_sampled): smp.noise and, when given, smp.samples are the step's rows
 // [N][A] of the call's noise and samples_out; a thread reads its element of the one and then
 // writes the same element of the other, so the two may be one buffer.
+// A drawn step (scg_sc_rollout_drawn) passes an ScDrawView for smp: the same, with the element not
+// read but computed (sc_drawn_noise: element (n, q) of the step's row).
 constexpr int kPolicyActBlock = 256;
 constexpr int kPolicyActChunk = 16;
-template <bool kSampled>
+__device__ __forceinline__ float sc_drawn_noise(const ScDrawView& drw, int64_t n, int q) {
+  return sc_noise_element(drw.k0, drw.k1, drw.row0, drw.env0 + static_cast<uint32_t>(n), static_cast<uint32_t>(q));
+}
+template <bool kSampled, class Noise>
 __device__ __forceinline__ void sc_policy_act(const ScPolicyView& pv, const void* obs, int obs_f64, int64_t N, int A, int O,
-                                              float* out0, float* out1, const ScSampleView& smp) {
+                                              float* out0, float* out1, const Noise& smp) {
   const int64_t id = static_cast<int64_t>(blockIdx.x) * kPolicyActBlock + threadIdx.x;
   if (id >= N * A) return;
   const int q = static_cast<int>(id / N);
   const int64_t n = id - static_cast<int64_t>(q) * N;
   [[maybe_unused]] float sd, e, u;  // the sampled body's alone: set and read only under kSampled
-  if constexpr (kSampled) sd = smp.std[q], e = smp.noise[n * A + q];
+  if constexpr (std::is_same_v<Noise, ScDrawView>) {
+    sd = smp.std[q], e = sc_drawn_noise(smp, n, q);
+  } else if constexpr (kSampled) {
+    sd = smp.std[q], e = smp.noise[n * A + q];
+  }
   float* const u_out = &u;
   const float act = sc_with_obs_row(obs, obs_f64, n, O, [=, &pv](auto o) {
     if constexpr (kSampled) {
@@ -75,7 +86,7 @@ __device__ __forceinline__ void sc_policy_act(const ScPolicyView& pv, const void
     if (smp.samples) smp.samples[n * A + q] = u;
 }
 
-// The two kernels of it: the deterministic one takes no noise arguments.
+// The three kernels of it: the deterministic one takes no noise arguments.
 __global__ __launch_bounds__(kPolicyActBlock) void sc_policy_act_kernel(const ScPolicyView pv, const void* obs, int obs_f64,
                                                                          int64_t N, int A, int O, float* out0, float* out1) {
   sc_policy_act<false>(pv, obs, obs_f64, N, A, O, out0, out1, ScSampleView{});
@@ -85,6 +96,11 @@ __global__ __launch_bounds__(kPolicyActBlock) void sc_policy_act_sampled_kernel(
                                                                                  float* out0, float* out1, const float* std,
                                                                                  const float* eps, float* samples) {
   sc_policy_act<true>(pv, obs, obs_f64, N, A, O, out0, out1, ScSampleView{std, eps, samples});
+}
+__global__ __launch_bounds__(kPolicyActBlock) void sc_policy_act_drawn_kernel(const ScPolicyView pv, const void* obs, int obs_f64,
+                                                                               int64_t N, int A, int O, float* out0, float* out1,
+                                                                               const ScDrawView drw) {
+  sc_policy_act<true>(pv, obs, obs_f64, N, A, O, out0, out1, drw);
 }
 
 // sum = (add ? sum : 0.0) + r: the per-step path's reward_sum.
@@ -104,9 +120,9 @@ __global__ __launch_bounds__(kPolicyActBlock) void sc_reward_sum_kernel(double* 
 constexpr int kMlpActBlock = 64;
 constexpr int kMlpActChunk = 16;
 // kSampled: smp as sc_policy_act's, the env's row read and written by the env's thread.
-template <bool kSampled>
+template <bool kSampled, class Noise>
 __device__ __forceinline__ void sc_mlp_act(const ScMlpView& mv, const void* obs, int obs_f64, int64_t N, int A, int O,
-                                           float* out0, float* out1, const ScSampleView& smp) {
+                                           float* out0, float* out1, const Noise& smp) {
   extern __shared__ float hid_t[];  // [H][64]
   const int64_t n = static_cast<int64_t>(blockIdx.x) * kMlpActBlock + threadIdx.x;
   if (n >= N) return;
@@ -118,7 +134,9 @@ __device__ __forceinline__ void sc_mlp_act(const ScMlpView& mv, const void* obs,
   for (int q = 0; q < A; ++q) {
     [[maybe_unused]] float u;
     float act;
-    if constexpr (kSampled) {
+    if constexpr (std::is_same_v<Noise, ScDrawView>) {
+      act = sc_mlp_action_sampled<kMlpActChunk>(mv, O, n, q, h, smp.std[q], sc_drawn_noise(smp, n, q), &u);
+    } else if constexpr (kSampled) {
       act = sc_mlp_action_sampled<kMlpActChunk>(mv, O, n, q, h, smp.std[q], smp.noise[n * A + q], &u);
     } else {
       act = sc_mlp_action<kMlpActChunk>(mv, O, n, q, h);
@@ -130,7 +148,7 @@ __device__ __forceinline__ void sc_mlp_act(const ScMlpView& mv, const void* obs,
   }
 }
 
-// The two kernels of it. (Four waves per SIMD: at most 128 VGPRs, as the node-parallel kernels.)
+// The three kernels of it. (Four waves per SIMD: at most 128 VGPRs, as the node-parallel kernels.)
 __global__ __launch_bounds__(kMlpActBlock) __attribute__((amdgpu_waves_per_eu(4)))
 void sc_mlp_act_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1) {
   sc_mlp_act<false>(mv, obs, obs_f64, N, A, O, out0, out1, ScSampleView{});
@@ -139,6 +157,41 @@ __global__ __launch_bounds__(kMlpActBlock) __attribute__((amdgpu_waves_per_eu(4)
 void sc_mlp_act_sampled_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0,
                                float* out1, const float* std, const float* eps, float* samples) {
   sc_mlp_act<true>(mv, obs, obs_f64, N, A, O, out0, out1, ScSampleView{std, eps, samples});
+}
+__global__ __launch_bounds__(kMlpActBlock) __attribute__((amdgpu_waves_per_eu(4)))
+void sc_mlp_act_drawn_kernel(const ScMlpView mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0,
+                             float* out1, const ScDrawView drw) {
+  sc_mlp_act<true>(mv, obs, obs_f64, N, A, O, out0, out1, drw);
+}
+
+// Rows of the drawn loop's noise as a tensor (scg_sc_noise_fill): thread id is group g = id % G of
+// element row id / G of out [K * N][A], G = ceil(A / 4) groups of 4 consecutive actions: one
+// Philox block, both pairs, up to four stores next to the neighbouring threads'.
+constexpr int kNoiseFillBlock = 256;
+__global__ __launch_bounds__(kNoiseFillBlock) void sc_noise_fill_kernel(float* out, int64_t rows, int64_t N, int A, int G,
+                                                                        uint32_t k0, uint32_t k1, uint32_t row0, uint32_t env0) {
+  const int64_t id = static_cast<int64_t>(blockIdx.x) * kNoiseFillBlock + threadIdx.x;
+  if (id >= rows * G) return;
+  const int64_t kn = id / G;
+  const int g = static_cast<int>(id - kn * G);
+  const int64_t k = kn / N, n = kn - k * N;
+  const U4 b = sc_noise_block(k0, k1, row0 + static_cast<uint32_t>(k), env0 + static_cast<uint32_t>(n), static_cast<uint32_t>(g));
+  const NormalPair p0 = normal_from_words(b.x, b.y), p1 = normal_from_words(b.z, b.w);
+  float* const o = out + kn * A + 4 * g;
+  const int left = A - 4 * g;
+  o[0] = p0.c;
+  if (left > 1) o[1] = p0.s;
+  if (left > 2) o[2] = p1.c;
+  if (left > 3) o[3] = p1.s;
+}
+
+// The transform alone on the caller's word pairs (scg_noise_from_words).
+__global__ __launch_bounds__(kNoiseFillBlock) void noise_from_words_kernel(const uint32_t* words, float* out, int64_t n) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kNoiseFillBlock + threadIdx.x;
+  if (i >= n) return;
+  const NormalPair p = normal_from_words(words[2 * i], words[2 * i + 1]);
+  out[2 * i] = p.c;
+  out[2 * i + 1] = p.s;
 }
 
 // Whether hidden units fit the LDS the fused kernel has idle for them (a config scg_sc_prepare
@@ -149,7 +202,8 @@ bool sc_mlp_fits(const scg_sc_config* cfg, int32_t hidden) {
 
 // What the closed loop's host body needs of a policy: its argument check, whether it fuses
 // beyond the linear condition, its view for the fused launch (sc_launch_nodes_closed) and the
-// launch of the action rows of one step (smp: the step's rows of a sampled call's noise, or null).
+// launch of the action rows of one step (smp: the step's rows of a sampled call's noise, drw: a
+// drawn call's noise at the step's row; at most one of them, or both null).
 struct LinearHost {
   const scg_sc_policy* pol;
   int check() const {
@@ -161,8 +215,12 @@ struct LinearHost {
   bool fits(const scg_sc_config*) const { return true; }
   ScPolicyView view(int64_t N) const { return sc_policy_view(pol->params, pol->shared != 0, N, pol->act_lo, pol->act_hi); }
   static int act(const ScPolicyView& pv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1,
-                 const ScSampleView* smp, hipStream_t s) {
+                 const ScSampleView* smp, const ScDrawView* drw, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>((N * A + kPolicyActBlock - 1) / kPolicyActBlock));
+    if (drw) {
+      hipLaunchKernelGGL(sc_policy_act_drawn_kernel, grid, dim3(kPolicyActBlock), 0, s, pv, obs, obs_f64, N, A, O, out0, out1, *drw);
+      return check_launch("sc_policy_act_drawn_kernel");
+    }
     if (smp) {
       hipLaunchKernelGGL(sc_policy_act_sampled_kernel, grid, dim3(kPolicyActBlock), 0, s, pv, obs, obs_f64, N, A, O, out0, out1,
                          smp->std, smp->noise, smp->samples);
@@ -188,9 +246,13 @@ struct MlpHost {
     return sc_mlp_view(pol->params, pol->shared != 0, N, pol->hidden, pol->act_lo, pol->act_hi);
   }
   static int act(const ScMlpView& mv, const void* obs, int obs_f64, int64_t N, int A, int O, float* out0, float* out1,
-                 const ScSampleView* smp, hipStream_t s) {
+                 const ScSampleView* smp, const ScDrawView* drw, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>((N + kMlpActBlock - 1) / kMlpActBlock));
     const size_t lds = sizeof(float) * kMlpActBlock * mv.H;
+    if (drw) {
+      hipLaunchKernelGGL(sc_mlp_act_drawn_kernel, grid, dim3(kMlpActBlock), lds, s, mv, obs, obs_f64, N, A, O, out0, out1, *drw);
+      return check_launch("sc_mlp_act_drawn_kernel");
+    }
     if (smp) {
       hipLaunchKernelGGL(sc_mlp_act_sampled_kernel, grid, dim3(kMlpActBlock), lds, s, mv, obs, obs_f64, N, A, O, out0, out1,
                          smp->std, smp->noise, smp->samples);
@@ -206,10 +268,11 @@ bool sc_closed_fused(const scg_sc_config* cfg, const scg_sc_state* st) {
   return cfg->kernel == SCG_SC_KERNEL_NODES && !st->ledger;
 }
 
-// smp: the call's noise (scg_sc_rollout_sampled), or null: the deterministic loop.
+// smp: the call's noise (scg_sc_rollout_sampled), draw: the noise it draws itself
+// (scg_sc_rollout_drawn); neither: the deterministic loop.
 template <class Policy>
 int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const Policy& policy,
-                      const scg_sc_sampling* smp, void* obs_io, float* act_work, float* actions_out, void* obs_out,
+                      const scg_sc_sampling* smp, const scg_sc_noise_draw* draw, void* obs_io, float* act_work, float* actions_out, void* obs_out,
                       double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags, int32_t* n_done,
                       void* stream) {
   if (int rc = sc_host_check(cfg, st)) return rc;
@@ -217,6 +280,12 @@ int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_step
   if (smp) {
     if (smp->reserved != 0) return fail(SCG_ERR_INVALID, "sampling: reserved must be 0");
     if (n_steps > 0 && (!smp->std || !smp->noise)) return fail(SCG_ERR_INVALID, "sampling: device std and noise are required");
+  }
+  if (draw) {
+    if (draw->reserved != 0) return fail(SCG_ERR_INVALID, "noise draw: reserved must be 0");
+    if (n_steps > 0 && !draw->std) return fail(SCG_ERR_INVALID, "noise draw: device std is required");
+    if (n_steps > 0 && static_cast<int64_t>(draw->row0) + n_steps > (int64_t(1) << 32))
+      return fail(SCG_ERR_INVALID, "noise draw: rows %u + %d pass 2^32", draw->row0, n_steps);
   }
   if (!obs_io || !act_work || !reward_sum) return fail(SCG_ERR_INVALID, "obs_io/act_work/reward_sum buffers are required");
   if (n_steps < 0) return fail(SCG_ERR_INVALID, "rollout of %d steps", n_steps);
@@ -245,6 +314,13 @@ int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_step
     const int64_t at = sc_sample_index(N, A, k, 0, 0);
     return ScSampleView{smp->std, smp->noise + at, smp->samples_out ? smp->samples_out + at : nullptr};
   };
+  // the same of a drawn call: its samples' rows and the global index of row k
+  auto drawn_rows = [&](int32_t k) {
+    const int64_t at = sc_sample_index(N, A, k, 0, 0);
+    return ScDrawView{draw->std, draw->samples_out ? draw->samples_out + at : nullptr, static_cast<uint32_t>(draw->seed),
+                      static_cast<uint32_t>(draw->seed >> 32), draw->row0 + static_cast<uint32_t>(k),
+                      static_cast<uint32_t>(st->env_offset)};
+  };
   int32_t crossed = 0;
   if (n_done) *n_done = 0;
   if (n_steps == 0) {
@@ -259,7 +335,9 @@ int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_step
       const void* src = (k == 0 || !oo) ? obs_io : oo + obs_row * (k - 1);
       float* const arow = actions_out ? actions_out + static_cast<int64_t>(k) * N * A : nullptr;
       const ScSampleView row = smp ? rows(k) : ScSampleView{};
-      if (int rc = Policy::act(pv, src, cfg->obs_f64, N, A, O, act_work, arow, smp ? &row : nullptr, s)) return rc;
+      const ScDrawView drow = draw ? drawn_rows(k) : ScDrawView{};
+      if (int rc = Policy::act(pv, src, cfg->obs_f64, N, A, O, act_work, arow, smp ? &row : nullptr, draw ? &drow : nullptr, s))
+        return rc;
       int32_t done = 0;
       double* const rrow = rewards_out + static_cast<int64_t>(k) * N;
       if (int rc = scg_sc_step(cfg, st, act_work, oo ? static_cast<void*>(oo + obs_row * k) : obs_io, rrow, terminal_obs,
@@ -289,8 +367,9 @@ int sc_rollout_closed(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_step
     float* const arows = actions_out ? actions_out + static_cast<int64_t>(k0) * N * A : nullptr;
     const ScClosedLaunch<decltype(pv)> p{pv, obs_io, act_work, arows, reward_sum, k0 > 0 ? 1 : 0};
     const int W = cfg->group, E = cfg->inbox_size;
-    if (int rc = smp ? sc_launch_nodes_closed(a, ScSampledLaunch<decltype(pv)>{p, rows(k0)}, maxd, W, E, kc, s)
-                     : sc_launch_nodes_closed(a, p, maxd, W, E, kc, s))
+    if (int rc = draw  ? sc_launch_nodes_closed(a, ScDrawnLaunch<decltype(pv)>{p, drawn_rows(k0)}, maxd, W, E, kc, s)
+                 : smp ? sc_launch_nodes_closed(a, ScSampledLaunch<decltype(pv)>{p, rows(k0)}, maxd, W, E, kc, s)
+                       : sc_launch_nodes_closed(a, p, maxd, W, E, kc, s))
       return rc;
     const int64_t end = static_cast<int64_t>(st->time_step) + kc;  // <= T without auto-reset
     if (reset) {
@@ -327,14 +406,14 @@ int scg_sc_observe(const scg_sc_config* cfg, const scg_sc_state* st, void* obs, 
 int scg_sc_rollout_policy(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_policy* policy,
                           void* obs_io, float* act_work, float* actions_out, void* obs_out, double* rewards_out,
                           double* reward_sum, void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
-  return sc_rollout_closed(cfg, st, n_steps, LinearHost{policy}, nullptr, obs_io, act_work, actions_out, obs_out, rewards_out,
+  return sc_rollout_closed(cfg, st, n_steps, LinearHost{policy}, nullptr, nullptr, obs_io, act_work, actions_out, obs_out, rewards_out,
                            reward_sum, terminal_obs, flags, n_done, stream);
 }
 
 int scg_sc_rollout_mlp(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_mlp* mlp, void* obs_io,
                        float* act_work, float* actions_out, void* obs_out, double* rewards_out, double* reward_sum,
                        void* terminal_obs, uint32_t flags, int32_t* n_done, void* stream) {
-  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, nullptr, obs_io, act_work, actions_out, obs_out, rewards_out, reward_sum,
+  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, nullptr, nullptr, obs_io, act_work, actions_out, obs_out, rewards_out, reward_sum,
                            terminal_obs, flags, n_done, stream);
 }
 
@@ -345,10 +424,50 @@ int scg_sc_rollout_sampled(const scg_sc_config* cfg, scg_sc_state* st, int32_t n
   if (!linear == !mlp) return fail(SCG_ERR_INVALID, "sampled rollout: exactly one of the linear policy and the mlp");
   if (!smp) return fail(SCG_ERR_INVALID, "sampled rollout: the sampling struct is required");
   if (linear)
-    return sc_rollout_closed(cfg, st, n_steps, LinearHost{linear}, smp, obs_io, act_work, actions_out, obs_out, rewards_out,
+    return sc_rollout_closed(cfg, st, n_steps, LinearHost{linear}, smp, nullptr, obs_io, act_work, actions_out, obs_out, rewards_out,
                              reward_sum, terminal_obs, flags, n_done, stream);
-  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, smp, obs_io, act_work, actions_out, obs_out, rewards_out, reward_sum,
+  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, smp, nullptr, obs_io, act_work, actions_out, obs_out, rewards_out, reward_sum,
                            terminal_obs, flags, n_done, stream);
+}
+
+int scg_sc_rollout_drawn(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps, const scg_sc_policy* linear,
+                         const scg_sc_mlp* mlp, const scg_sc_noise_draw* draw, void* obs_io, float* act_work, float* actions_out,
+                         void* obs_out, double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags,
+                         int32_t* n_done, void* stream) {
+  if (!linear == !mlp) return fail(SCG_ERR_INVALID, "drawn rollout: exactly one of the linear policy and the mlp");
+  if (!draw) return fail(SCG_ERR_INVALID, "drawn rollout: the noise draw struct is required");
+  if (linear)
+    return sc_rollout_closed(cfg, st, n_steps, LinearHost{linear}, nullptr, draw, obs_io, act_work, actions_out, obs_out,
+                             rewards_out, reward_sum, terminal_obs, flags, n_done, stream);
+  return sc_rollout_closed(cfg, st, n_steps, MlpHost{mlp}, nullptr, draw, obs_io, act_work, actions_out, obs_out, rewards_out,
+                           reward_sum, terminal_obs, flags, n_done, stream);
+}
+
+int scg_sc_noise_fill(const scg_sc_config* cfg, const scg_sc_state* st, uint64_t seed, uint32_t row0, int32_t n_rows, float* out,
+                      void* stream) {
+  if (int rc = sc_host_check(cfg, st)) return rc;
+  if (n_rows < 0 || static_cast<int64_t>(row0) + n_rows > (int64_t(1) << 32))
+    return fail(SCG_ERR_INVALID, "noise fill: rows %u + %d", row0, n_rows);
+  if (n_rows == 0) return SCG_OK;
+  if (!out) return fail(SCG_ERR_INVALID, "noise fill: the out buffer is required");
+  const int A = cfg->n_actions, G = (A + 3) / 4;
+  const int64_t rows = static_cast<int64_t>(n_rows) * st->n_envs;
+  const int64_t blocks = (rows * G + kNoiseFillBlock - 1) / kNoiseFillBlock;
+  if (blocks > 0x7fffffff) return fail(SCG_ERR_INVALID, "noise fill: %lld blocks", static_cast<long long>(blocks));
+  hipLaunchKernelGGL(sc_noise_fill_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kNoiseFillBlock), 0,
+                     static_cast<hipStream_t>(stream), out, rows, st->n_envs, A, G, static_cast<uint32_t>(seed),
+                     static_cast<uint32_t>(seed >> 32), row0, static_cast<uint32_t>(st->env_offset));
+  return check_launch("sc_noise_fill_kernel");
+}
+
+int scg_noise_from_words(const uint32_t* words, float* out, int64_t n, void* stream) {
+  if (n < 0 || (n > 0 && (!words || !out))) return fail(SCG_ERR_INVALID, "noise from words: device words and out are required");
+  if (n == 0) return SCG_OK;
+  const int64_t blocks = (n + kNoiseFillBlock - 1) / kNoiseFillBlock;
+  if (blocks > 0x7fffffff) return fail(SCG_ERR_INVALID, "noise from words: %lld pairs", static_cast<long long>(n));
+  hipLaunchKernelGGL(noise_from_words_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kNoiseFillBlock), 0,
+                     static_cast<hipStream_t>(stream), words, out, n);
+  return check_launch("noise_from_words_kernel");
 }
 
 int scg_sc_mlp_fused(const scg_sc_config* cfg, const scg_sc_state* st, int32_t hidden) {

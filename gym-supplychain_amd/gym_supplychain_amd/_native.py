@@ -168,6 +168,12 @@ class ScSampling(ctypes.Structure):
                 ("reserved", ctypes.c_int64)]
 
 
+class ScNoiseDraw(ctypes.Structure):
+    """scg_sc_noise_draw (include/scgpu.h): the std, samples, seed and first row of scg_sc_rollout_drawn."""
+    _fields_ = [("std", ctypes.c_void_p), ("samples_out", ctypes.c_void_p), ("seed", ctypes.c_uint64),
+                ("row0", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class BgServerLine(ctypes.Structure):
     """scg_bg_server_line (include/scgpu.h): one slot's 64-byte request line."""
     _fields_ = [("req_seq", ctypes.c_uint32), ("cmd", ctypes.c_int32), ("wpack", ctypes.c_uint32),
@@ -236,6 +242,7 @@ SC_KERNEL_AUTO, SC_KERNEL_LANE, SC_KERNEL_LEVEL, SC_KERNEL_STAGED, SC_KERNEL_NOD
 SC_LAYOUT_ENV_FASTEST, SC_LAYOUT_ENV_MAJOR = 0, 1
 SCG_STREAM_SC_DEMAND = 2
 SCG_STREAM_SC_LEADTIME = 3
+SCG_STREAM_SC_NOISE = 6
 
 _PA = ctypes.c_int32 * SC_MAX_PRODUCTS
 
@@ -354,6 +361,14 @@ SIGNATURES = {
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _i32p,
                                               ctypes.c_void_p]),
+    "scg_sc_rollout_drawn": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_int32,
+                                            ctypes.POINTER(ScPolicy), ctypes.POINTER(ScMlp), ctypes.POINTER(ScNoiseDraw),
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _i32p,
+                                            ctypes.c_void_p]),
+    "scg_sc_noise_fill": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_uint64,
+                                         ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "scg_noise_from_words": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "scg_sc_draw_tables": (ctypes.c_int, [ctypes.POINTER(ScConfig), ctypes.POINTER(ScState), ctypes.c_uint32,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_nodes_max_blocks": (ctypes.c_int, [ctypes.c_int32]),

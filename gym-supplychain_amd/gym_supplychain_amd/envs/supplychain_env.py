@@ -257,6 +257,8 @@ class SupplyChainVecEnv:
     rollout_policy(weights, bias, n_steps) -> ScPolicyRollout: K steps with a linear policy's actions computed on the device
     rollout_policy(pack_mlp(w1, b1, w2, b2), None, n_steps): the same with a one-hidden-layer ReLU policy
     rollout_policy(..., noise=eps, std=s, samples_out=u): either policy with sampled actions, clip(z + s * eps[k])
+    rollout_policy(..., noise_seed=s, noise_row=r, std=s, samples_out=u): the same with eps drawn on the device
+    draw_noise(noise_seed, n_steps, noise_row) -> eps [K, N, n_actions]: those rows as a tensor
     observe() -> obs [N, n_obs]: the current observation, whatever call left the state
 
     Returned tensors are this env's output buffers (clone() to keep them). With
@@ -620,10 +622,25 @@ class SupplyChainVecEnv:
             nat.check(-rc)
         return bool(rc)
 
-    def _sampling(self, K, noise, std, samples_out):
-        """The checked (noise, std on the device, samples_out) of a sampled rollout_policy call."""
+    @staticmethod
+    def _noise_rows(noise_seed, noise_row, K):
+        """The checked (seed, first row) of K rows of the noise the device draws."""
+        if isinstance(noise_seed, bool) or not isinstance(noise_seed, (int, np.integer)) or not 0 <= int(noise_seed) < 2 ** 64:
+            raise ValueError("noise_seed must be an integer in [0, 2^64)")
+        if isinstance(noise_row, bool) or not isinstance(noise_row, (int, np.integer)):
+            raise ValueError("noise_row must be an integer")
+        if int(noise_row) < 0 or int(noise_row) + K > 2 ** 32:
+            raise ValueError(f"noise rows {int(noise_row)} .. {int(noise_row) + K} must lie in [0, 2^32]")
+        return int(noise_seed), int(noise_row)
+
+    def _sampling(self, K, noise, std, samples_out, drawn=False):
+        """The checked (noise, std on the device, samples_out) of a sampled rollout_policy call
+        (drawn: the device draws the noise, and none is passed)."""
         N, A = self.n_envs, self.n_actions
-        if noise is None or std is None:
+        if drawn:
+            if std is None:
+                raise ValueError("noise_seed needs std")
+        elif noise is None or std is None:
             raise ValueError("noise and std go together" if noise is not None or std is not None else
                              "samples_out needs noise and std")
         for name, x in (("noise", noise), ("samples_out", samples_out)):
@@ -645,7 +662,7 @@ class SupplyChainVecEnv:
         return noise, sd.contiguous(), samples_out
 
     def rollout_policy(self, weights, bias=None, n_steps=None, clip=None, return_actions=False, return_obs=False,
-                       return_rewards=False, noise=None, std=None, samples_out=None):
+                       return_rewards=False, noise=None, std=None, samples_out=None, noise_seed=None, noise_row=0):
         """n_steps steps with every env's action row computed on the device from the
         observation o the env last produced (scg_sc_rollout_policy), all in float32, each
         multiply and add rounded on its own, in this order:
@@ -687,7 +704,14 @@ class SupplyChainVecEnv:
         pairs, OU noise). samples_out, None or a tensor like noise, receives u, what the
         log-probability is taken of; it may be noise itself, which is then overwritten. The
         result's `samples` is that tensor. A full episode of 360 steps of 65,536 envs with 14
-        actions is 1.3 GB of noise. Without noise the call is the deterministic one above."""
+        actions is 1.3 GB of noise. Without noise the call is the deterministic one above.
+
+        noise_seed, an int in [0, 2^64), instead of noise (never both; std is required): the device
+        draws the noise itself where it uses it (scg_sc_rollout_drawn), and no noise tensor exists.
+        Row k of the call is row noise_row + k of draw_noise(noise_seed, ...), whose docstring
+        defines every element; a caller who cuts an episode into several calls counts noise_row
+        on (0 <= noise_row, noise_row + n_steps <= 2^32). The loop is otherwise the one above, bit
+        for bit the call with noise=draw_noise(noise_seed, n_steps, noise_row)."""
         N, A, O = self.n_envs, self.n_actions, self.n_obs
         if isinstance(weights, (ScPackedPolicy, ScPackedMlp)):
             if bias is not None:
@@ -709,9 +733,14 @@ class SupplyChainVecEnv:
         if getattr(self, "_pol_obs", None) is None:  # the call's own buffers, kept for the next
             self._pol_obs = torch.empty((N, O), dtype=self.obs_dtype, device=dev)
             self._pol_act = torch.empty((N, A), dtype=torch.float32, device=dev)
-        sampled = noise is not None or std is not None or samples_out is not None
+        drawn = noise_seed is not None
+        if drawn and noise is not None:
+            raise ValueError("noise and noise_seed exclude each other")
+        sampled = drawn or noise is not None or std is not None or samples_out is not None
+        if drawn:
+            noise_seed, noise_row = self._noise_rows(noise_seed, noise_row, K)
         if sampled:
-            noise, std, samples_out = self._sampling(K, noise, std, samples_out)
+            noise, std, samples_out = self._sampling(K, noise, std, samples_out, drawn)
         mlp = isinstance(packed, ScPackedMlp)
         fused = self.mlp_fused(packed.hidden) if mlp else self.kernel == "nodes" and not self.build_info
         rewards = torch.empty((K, N), dtype=torch.float64, device=dev) if (return_rewards or not fused) else None
@@ -731,7 +760,13 @@ class SupplyChainVecEnv:
                                packed.params.data_ptr())
             entry = nat.lib.scg_sc_rollout_policy
         n_done = ctypes.c_int32(0)
-        if sampled:
+        if drawn:
+            drw = nat.ScNoiseDraw(std.data_ptr(), samples_out.data_ptr() if samples_out is not None else None,
+                                  noise_seed, noise_row, 0)
+            pols = (None, ctypes.byref(pol)) if mlp else (ctypes.byref(pol), None)
+            head = (*pols, ctypes.byref(drw))
+            entry = nat.lib.scg_sc_rollout_drawn
+        elif sampled:
             smp = nat.ScSampling(std.data_ptr(), noise.data_ptr(),
                                  samples_out.data_ptr() if samples_out is not None else None, 0)
             pols = (None, ctypes.byref(pol)) if mlp else (ctypes.byref(pol), None)
@@ -747,6 +782,35 @@ class SupplyChainVecEnv:
         if n_done.value:
             self.check_errors()
         return res
+
+    def draw_noise(self, noise_seed, n_steps, noise_row=0, out=None):
+        """Rows noise_row .. noise_row + n_steps - 1 of the noise rollout_policy(noise_seed=) draws,
+        float32 [n_steps, N, A] on the env's device (scg_sc_noise_fill; `out`, a contiguous tensor
+        of that kind, is filled and returned): for the learning pass, for chunked calls, for
+        tests. Element [k, n, a] is the project's own float32 standard normal (Box-Muller on
+        Philox4x32-10 words), with e = env_offset + n and row = noise_row + k:
+
+            blk      = philox4x32_10(ctr=(e, row, a >> 2, 6), key=(noise_seed & 0xffffffff, noise_seed >> 32))
+            (w1, w2) = (blk[0], blk[1]) if (a >> 1) & 1 == 0 else (blk[2], blk[3])
+            m = (w1 >> 8) + 1;  u = m * 2**-24  in (0, 1]
+            v = w2 >> 8;        theta = 2 * pi * v * 2**-24
+            eps = r * cos(theta) if a is even else r * sin(theta),   r = sqrt(-2 * ln(u))
+
+        r, cos and sin are computed from float32 + - * / sqrt alone, each rounded on its own
+        (csrc/scg_normal.h; tests/noise_ref.py states them in NumPy, bit for bit), within 7.9e-7
+        of the float64 value. A sharded env (env_offset) draws its rows of the unsharded batch."""
+        N, A = self.n_envs, self.n_actions
+        if n_steps is None or isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or int(n_steps) < 0:
+            raise ValueError("n_steps must be a non-negative integer")
+        K = int(n_steps)
+        noise_seed, noise_row = self._noise_rows(noise_seed, noise_row, K)
+        if out is None:
+            out = torch.empty((K, N, A), dtype=torch.float32, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.device or \
+                tuple(out.shape) != (K, N, A) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor [{K}, {N}, {A}] on {self.device}")
+        nat.check(nat.lib.scg_sc_noise_fill(self._cfg_ref, self._st_ref, noise_seed, noise_row, K, nat.ptr(out), self._stream()))
+        return out
 
     def _ledger_views(self, led, rewards):
         P, names = self.spec.P, nat.SC_LEDGER_NAMES

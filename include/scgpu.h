@@ -57,7 +57,9 @@ extern "C" {
  *   local-information policy on inventory position and orders), added entry points; also
  *   scg_bg_rollout_mlp (scg_bg_mlp: the same closed loop with a shared one-hidden-layer ReLU
  *   policy in float32 over the local features, deterministic or sampled from the caller's
- *   noise), an added entry point. */
+ *   noise), an added entry point; also scg_sc_rollout_drawn, scg_sc_noise_fill and the testing
+ *   hook scg_noise_from_words (scg_sc_noise_draw: the sampled SupplyChain closed loop with
+ *   its noise drawn on the device from a seed and a row counter), added entry points. */
 #define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
@@ -574,6 +576,7 @@ SCG_API int scg_uniform_ints(uint64_t seed, int64_t env_offset, int64_t n_envs, 
 #define SCG_SC_LAYOUT_ENV_MAJOR 1   /* stock [N][NP], heaps [N][NP][H], sizes [N][NP]          */
 #define SCG_STREAM_SC_DEMAND 2u
 #define SCG_STREAM_SC_LEADTIME 3u
+#define SCG_STREAM_SC_NOISE 6u /* the exploration noise a closed loop draws itself (scg_sc_noise_draw) */
 
 /* One chain node (SC_Node :106-206 after define_destinations), in nodes_info order. */
 typedef struct scg_sc_node {
@@ -874,6 +877,53 @@ SCG_API int scg_sc_rollout_sampled(const scg_sc_config* cfg, scg_sc_state* st, i
                                    void* obs_io, float* act_work, float* actions_out, void* obs_out,
                                    double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags,
                                    int32_t* n_done, void* stream);
+
+/*
+ * The sampled closed loop with the noise drawn on the device: scg_sc_rollout_sampled with
+ * eps[k][n][a] not read from memory but computed where it is used. Element (row k, env id e,
+ * action a) of the noise of a 64-bit seed is the project's own float32 standard normal
+ * (csrc/scg_normal.h, restated in NumPy by tests/noise_ref.py):
+ *   blk      = philox4x32_10(ctr = (e, k, a >> 2, SCG_STREAM_SC_NOISE), key = (seed & 0xffffffff, seed >> 32))
+ *   (w1, w2) = (blk.x, blk.y) for pair (a >> 1) & 1 == 0, (blk.z, blk.w) for pair 1
+ *   m = (w1 >> 8) + 1, u = m * 2^-24;   v = w2 >> 8, theta = 2 pi v * 2^-24;   r = sqrt(-2 ln u)
+ *   eps = r cos(theta) for even a, r sin(theta) for odd a
+ * with r, cos and sin from float32 + - * / sqrt alone, each rounded on its own (no FMA, no
+ * library function), so the host, the device and NumPy give the same bits; |eps - eps64| <= 7.9e-7
+ * against the float64 Box-Muller of the same (u, theta). The eps of step j of the call is
+ * element (row0 + j, env_offset + n, a): a sharded batch draws what the unsharded one draws, and
+ * a caller who cuts an episode into several calls passes each its own row0.
+ *   std          DEVICE float32 [n_actions], as scg_sc_sampling's
+ *   samples_out  DEVICE float32 [K][N][n_actions] or NULL: u before the clamp
+ *   seed         the noise's seed (its own: not the state's)
+ *   row0         the global row index of the call's first step
+ * Contract, flags, error codes and the choice of the fused or the per-step path are those of
+ * scg_sc_rollout_sampled. Checked before any HIP call, st left untouched: SCG_ERR_INVALID for a
+ * NULL draw, for a NULL std with n_steps > 0, for reserved != 0, for row0 + n_steps > 2^32, and
+ * for everything scg_sc_rollout_sampled refuses.
+ */
+typedef struct scg_sc_noise_draw {
+  const float* std;    /* DEVICE float32 [n_actions] */
+  float* samples_out;  /* DEVICE float32 [K][N][n_actions] or NULL */
+  uint64_t seed;
+  uint32_t row0;
+  uint32_t reserved;   /* 0 */
+} scg_sc_noise_draw;   /* 32 bytes */
+
+SCG_API int scg_sc_rollout_drawn(const scg_sc_config* cfg, scg_sc_state* st, int32_t n_steps,
+                                 const scg_sc_policy* linear, const scg_sc_mlp* mlp, const scg_sc_noise_draw* draw,
+                                 void* obs_io, float* act_work, float* actions_out, void* obs_out,
+                                 double* rewards_out, double* reward_sum, void* terminal_obs, uint32_t flags,
+                                 int32_t* n_done, void* stream);
+
+/* Rows row0 .. row0 + n_rows - 1 of that noise for the state's envs, into out DEVICE float32
+ * [n_rows][N][n_actions] (the learning pass regenerates what the rollout drew). SCG_ERR_INVALID
+ * for a NULL out with n_rows > 0, n_rows < 0 or row0 + n_rows > 2^32. */
+SCG_API int scg_sc_noise_fill(const scg_sc_config* cfg, const scg_sc_state* st, uint64_t seed, uint32_t row0,
+                              int32_t n_rows, float* out, void* stream);
+
+/* Testing hook: the device transform on the caller's Philox word pairs, words DEVICE uint32
+ * [n][2] = (w1, w2) into out DEVICE float32 [n][2] = (r cos, r sin). */
+SCG_API int scg_noise_from_words(const uint32_t* words, float* out, int64_t n, void* stream);
 
 /* The per-episode tables scg_sc_step draws (for tests): demand DEVICE int32
  * [N][T+1][R][P], leadtimes DEVICE int32 [N][T][n_leadtimes] (NULL when deterministic). */
