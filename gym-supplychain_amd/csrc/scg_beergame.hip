@@ -651,7 +651,7 @@ int scg_bg_rollout(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, 
   });
 }
 
-// ---- the closed loop: scg_bg_rollout_policy, _local and _mlp ------------------------------
+// ---- the closed loop: scg_bg_rollout_policy, _local, _mlp and _drawn -----------------------
 // What the in-transit sum needs of a config: every delay within the 64-bit live mask, and the
 // ring (a full table keeps rows past T, which would need a different rule).
 static int check_local_config(const scg_bg_config* cfg) {
@@ -677,10 +677,10 @@ static int32_t local_last_fixed(const scg_bg_config* cfg, int32_t w0) {
   return (cfg->demand_mode == SCG_DEMAND_FIXED && w0 >= 1) ? cfg->customer_demand[w0 - 1] : 0;
 }
 
-// The one host path of the three entry points. `who` names the policy in the messages; validate()
-// checks what is particular to the policy struct; fill(src, done) sets what is particular to the
-// source, for the launch that starts `done` action words into the call's per-week buffers. The
-// order of the checks is behaviour (tests/test_bg_closed_abi.py).
+// The one host path of the four entry points. `who` names the policy in the messages; validate()
+// checks what is particular to the policy struct; fill(src, done, done_k) sets what is particular to
+// the source, for the launch that starts at week done_k of the call, `done` action words into the
+// call's per-week buffers. The order of the checks is behaviour (tests/test_bg_closed_abi.py).
 extern "C++" {
 template <class Source, class Policy, class Validate, class Fill>
 static int closed_rollout(const char* who, int32_t kind, const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks,
@@ -716,7 +716,7 @@ static int closed_rollout(const char* who, int32_t kind, const scg_bg_config* cf
     src.first = done_k == 0;
     if constexpr (Source::kLocal)  // st->week: the state this launch starts from (weeks.wk[0].week - 1)
       src.start = LocalStart{local_last_fixed(cfg, st->week), local_mask(cfg, st->week)};
-    fill(src, done);
+    fill(src, done, done_k);
     return bg_launch_closed(cfg->levels, cfg->variant, grid_for(st->n_envs), s, a, K, weeks, src);
   });
 }
@@ -733,7 +733,7 @@ static int int_policy_rollout(const char* who, int32_t kind, const scg_bg_config
         return fail(SCG_ERR_INVALID, "%s needs shift in 0..%d and act_lo <= act_hi (got shift=%d, clamp %d..%d)", who,
                     kPolicyMaxShift, p->shift, p->act_lo, p->act_hi);
       },
-      [&](Source& src, int64_t) { src.clamp = PolicyClamp{p->shift, p->act_lo, p->act_hi}; });
+      [&](Source& src, int64_t, int32_t) { src.clamp = PolicyClamp{p->shift, p->act_lo, p->act_hi}; });
 }
 }  // extern "C++"
 
@@ -765,7 +765,7 @@ int scg_bg_rollout_mlp(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_wee
         if (policy->samples_out && !policy->noise) return fail(SCG_ERR_INVALID, "MLP policy: samples_out needs noise and std");
         return SCG_OK;
       },
-      [&](MlpArgs& ma, int64_t done) {
+      [&](MlpArgs& ma, int64_t done, int32_t) {
         ma.std = policy->std;
         ma.noise = policy->noise ? policy->noise + done : nullptr;
         ma.samples_out = policy->samples_out ? policy->samples_out + done : nullptr;
@@ -774,6 +774,52 @@ int scg_bg_rollout_mlp(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_wee
         ma.lo = policy->act_lo;
         ma.hi = policy->act_hi;
       });
+}
+
+// The sampled MLP loop with the noise computed by the lanes: the launch that starts at week done_k
+// of the call gets first row row0 + done_k.
+int scg_bg_rollout_drawn(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_mlp* policy,
+                         const scg_bg_noise_draw* draw, int32_t* actions_out, int32_t* obs, int32_t* rewards,
+                         int64_t* reward_sum, uint32_t flags, void* stream) {
+  return closed_rollout<MlpDrawnArgs>(
+      "MLP policy", SCG_BG_POLICY_MLP, cfg, st, n_weeks, policy, actions_out, obs, rewards, reward_sum, flags, stream,
+      [&]() -> int {
+        if (!bg_mlp_valid(policy->kind, policy->hidden, policy->act_lo, policy->act_hi))
+          return fail(SCG_ERR_INVALID,
+                      "MLP policy needs hidden in 1..%d and -2^24 <= act_lo <= act_hi <= 2^24 (got hidden=%d, clamp %d..%d)",
+                      kBgMlpMaxHidden, policy->hidden, policy->act_lo, policy->act_hi);
+        if (!draw) return fail(SCG_ERR_INVALID, "noise draw: null draw");
+        if (draw->reserved != 0) return fail(SCG_ERR_INVALID, "noise draw: reserved must be 0");
+        if (policy->noise) return fail(SCG_ERR_INVALID, "noise draw: the policy's noise must be NULL");
+        if (n_weeks > 0 && !policy->std) return fail(SCG_ERR_INVALID, "noise draw: device std is required");
+        if (n_weeks > 0 && static_cast<int64_t>(draw->row0) + n_weeks > (int64_t(1) << 32))
+          return fail(SCG_ERR_INVALID, "noise draw: rows %u + %d pass 2^32", draw->row0, n_weeks);
+        return SCG_OK;
+      },
+      [&](MlpDrawnArgs& da, int64_t done, int32_t done_k) {
+        da.std = policy->std;
+        da.samples_out = policy->samples_out ? policy->samples_out + done : nullptr;
+        da.features_out = policy->features_out ? policy->features_out + done * kLocalFeatures : nullptr;
+        da.hidden = policy->hidden;
+        da.lo = policy->act_lo;
+        da.hi = policy->act_hi;
+        da.key0 = static_cast<uint32_t>(draw->seed & 0xffffffffu);
+        da.key1 = static_cast<uint32_t>(draw->seed >> 32);
+        da.row0 = draw->row0 + static_cast<uint32_t>(done_k);
+      });
+}
+
+int scg_bg_noise_fill(const scg_bg_config* cfg, const scg_bg_state* st, uint64_t seed, uint32_t row0, int32_t n_rows,
+                      float* out, void* stream) {
+  if (int rc = check_state(cfg, st)) return rc;
+  if (cfg->levels > SCG_BG_POLICY_MAX_LEVELS)
+    return fail(SCG_ERR_INVALID, "noise fill: levels=%d above %d", cfg->levels, SCG_BG_POLICY_MAX_LEVELS);
+  if (n_rows < 0 || static_cast<int64_t>(row0) + n_rows > (int64_t(1) << 32))
+    return fail(SCG_ERR_INVALID, "noise fill: rows %u + %d", row0, n_rows);
+  if (n_rows == 0) return SCG_OK;
+  if (!out) return fail(SCG_ERR_INVALID, "noise fill: the out buffer is required");
+  return bg_launch_noise_fill(static_cast<hipStream_t>(stream), cfg->levels, st->n_envs, n_rows, static_cast<uint32_t>(seed & 0xffffffffu),
+                              static_cast<uint32_t>(seed >> 32), row0, static_cast<uint32_t>(st->env_offset), out);
 }
 
 int scg_bg_local_features(const scg_bg_config* cfg, const scg_bg_state* st, int32_t* out, void* stream) {

@@ -40,6 +40,7 @@
 #include "scg_common.h"
 #include "scg_mailbox.h"
 #include "scg_const.h"
+#include "scg_normal.h"
 #include "scg_philox.h"
 #include "scgpu.h"
 
@@ -1002,6 +1003,8 @@ constexpr int kRolloutGroup = 8;
 struct RolloutActs {
   static constexpr bool kPolicy = false;
   static constexpr bool kLocal = false;
+  static constexpr bool kMlp = false;
+  static constexpr bool kDrawn = false;
   static constexpr int kGroup = kRolloutGroup;
   template <int L>
   struct Regs {};
@@ -1023,6 +1026,8 @@ template <class Param>
 struct ClosedOut {
   static constexpr bool kPolicy = true;
   static constexpr bool kLocal = false;
+  static constexpr bool kMlp = false;    // the float32 MLP: the body states it once for its sources
+  static constexpr bool kDrawn = false;  // an MLP source that computes its noise row
   static constexpr int kGroup = 1;
   const Param* params;  // the policy's, in its own layout
   int32_t* acts_out;    // [K][N][L] of this launch, or null
@@ -1077,6 +1082,7 @@ struct LocalArgs : ClosedOut<int32_t> {
 // closed_act, for the time that form cost (profiles/r19a_bg_closed_consolidation_isa.txt).
 struct MlpArgs : ClosedOut<float> {
   static constexpr bool kLocal = true;
+  static constexpr bool kMlp = true;
   template <int L>
   using Regs = float[L];  // the standard deviations
   const float* std;       // [L]; non-null when noise is
@@ -1093,6 +1099,35 @@ __device__ __forceinline__ void closed_load(const MlpArgs& src, int64_t, int64_t
   for (int l = 0; l < L; ++l) sd[l] = src.noise ? const_tab(src.std)[l] : 0.0f;
 }
 static_assert(sizeof(PolicyArgs) == 56 && sizeof(LocalArgs) == 72 && sizeof(MlpArgs) == 104, "the kernel arguments' bytes");
+__device__ __forceinline__ bool mlp_sampled(const MlpArgs& src) { return src.noise != nullptr; }
+
+// MlpDrawn: MlpArgs' sampled loop with no noise tensor (scg_bg_rollout_drawn). Week k's row is
+// computed at the top of the week, where MlpArgs requests its row: elements (row0 + k, env id,
+// 0 .. L-1) of the noise of key (key0, key1), bg_noise_row of scg_normal.h. The row depends on
+// nothing of the state; its VALU work was measured 0.74 us per week above the read of a tensor
+// already there (L = 4). A launch of this source always samples.
+struct MlpDrawnArgs : ClosedOut<float> {
+  static constexpr bool kLocal = true;
+  static constexpr bool kMlp = true;
+  static constexpr bool kDrawn = true;
+  template <int L>
+  using Regs = float[L];  // the standard deviations
+  const float* std;       // [L]
+  float* samples_out;     // [K][N][L] of this launch (u), or null
+  int32_t* features_out;  // [K][N][L][4] of this launch, or null
+  int32_t hidden, lo, hi;
+  int32_t first;
+  LocalStart start;
+  uint32_t key0, key1;  // seed & 0xffffffff, seed >> 32
+  uint32_t row0;        // the global row of the launch's first week
+};
+template <int L>
+__device__ __forceinline__ void closed_load(const MlpDrawnArgs& src, int64_t, int64_t, float (&sd)[L]) {
+#pragma unroll
+  for (int l = 0; l < L; ++l) sd[l] = const_tab(src.std)[l];
+}
+static_assert(sizeof(MlpDrawnArgs) == 112, "the kernel arguments' bytes");
+__device__ __forceinline__ bool mlp_sampled(const MlpDrawnArgs&) { return true; }
 
 // The week's action of an integer policy, from the observation o the env last produced or (kLocal)
 // the features f of its state.
@@ -1155,7 +1190,8 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
   const int64_t stride = a.n * L;
   constexpr bool kPolicy = Source::kPolicy;
   constexpr bool kLocal = Source::kLocal;
-  constexpr bool kMlp = std::is_same_v<Source, MlpArgs>;  // the one source the body knows by name
+  constexpr bool kMlp = Source::kMlp;
+  constexpr bool kDrawn = Source::kDrawn;
   [[maybe_unused]] typename Source::template Regs<L> regs;
   if constexpr (kPolicy) closed_load(src, a.n, n, regs);
   int32_t inv[L], bk[L], op[L], iacc[L], bacc[L], pacc[L];
@@ -1210,8 +1246,14 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
       int32_t due[L], obs[L], ship[L], cur[L];
       int32_t(&act)[L] = group_act[u];
       [[maybe_unused]] int32_t eps[L];  // the MLP's noise row of the week, as bits
-      if constexpr (kMlp)
+      if constexpr (kDrawn) {
+        float e[L];
+        bg_noise_row<L>(src.key0, src.key1, src.row0 + static_cast<uint32_t>(k), static_cast<uint32_t>(a.env_offset + n), e);
+#pragma unroll
+        for (int l = 0; l < L; ++l) eps[l] = __float_as_int(e[l]);
+      } else if constexpr (kMlp) {
         if (src.noise) load_row<L>(reinterpret_cast<const int32_t*>(src.noise) + k * stride + row, eps);
+      }
       if constexpr (kPolicy) {
         int32_t o[L];
         policy_obs<L>(inv, bk, kV2 ? a.max_stock : 0, o);
@@ -1224,7 +1266,7 @@ __device__ __forceinline__ void rollout_body(const BgArgs& a, int64_t n, int32_t
           }
           float z[L];
           bg_mlp_z<L>(const_tab(src.params), src.hidden, f, z);
-          if (src.noise) {
+          if (mlp_sampled(src)) {
             int32_t ubits[L];
 #pragma unroll
             for (int l = 0; l < L; ++l) {
@@ -1365,10 +1407,16 @@ __global__ __launch_bounds__(kBlock) void bg_rollout_kernel(const BgArgs a, int3
 }
 
 // A closed-loop source's rollout at L levels (1..SCG_BG_POLICY_MAX_LEVELS): defined in
-// scg_bg_closed_launch.h, instantiated in scg_bg_policy.hip, scg_bg_local.hip and scg_bg_mlp.hip.
+// scg_bg_closed_launch.h, instantiated in scg_bg_policy.hip, scg_bg_local.hip, scg_bg_mlp.hip and
+// scg_bg_drawn.hip.
 template <class Source>
 int bg_launch_closed(int L, int variant, dim3 grid, hipStream_t s, const BgArgs& a, int32_t K, const RolloutWeeks& weeks,
                      const Source& src);
+
+// Rows row0 .. of the drawn loop's noise for the state's envs (out [rows][N][L]); defined in
+// scg_bg_drawn.hip.
+int bg_launch_noise_fill(hipStream_t s, int L, int64_t N, int64_t rows, uint32_t k0, uint32_t k1, uint32_t row0,
+                         uint32_t env0, float* out);
 
 // The local features of the state as it stands (out [N][L][4]; w0 = st->week, `live` its mask,
 // last_fixed as in LocalStart); defined in scg_bg_local.hip.

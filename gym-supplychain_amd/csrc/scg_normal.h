@@ -1,7 +1,9 @@
 // The project's float32 standard normal, host and device (no HIP runtime header: a host program
 // can include this alone). It is the one definition of the exploration noise a closed loop draws
-// itself (include/scgpu.h scg_sc_noise_draw, scg_sc_noise_fill), restated in NumPy by
-// tests/noise_ref.py. Element (row k, env id e, action a) of a 64-bit seed:
+// itself (include/scgpu.h scg_sc_noise_draw, scg_sc_noise_fill, scg_bg_noise_draw,
+// scg_bg_noise_fill), restated in NumPy by tests/noise_ref.py. The stream serves both env
+// families (a BeerGame action a is level a): a BeerGame and a SupplyChain env given the same seed
+// draw the same numbers. Element (row k, env id e, action a) of a 64-bit seed:
 //
 //   blk      = philox4x32_10(ctr = (e, k, a >> 2, SCG_STREAM_SC_NOISE), key = (seed & 0xffffffff, seed >> 32))
 //   (w1, w2) = (blk.x, blk.y) for pair (a >> 1) & 1 == 0, (blk.z, blk.w) for pair 1
@@ -131,6 +133,29 @@ __host__ __device__ __forceinline__ float sc_noise_element(uint32_t k0, uint32_t
   const U4 b = sc_noise_block(k0, k1, row, env, a >> 2);
   const bool second = (a >> 1) & 1u;
   return normal_from_words_one(second ? b.z : b.x, second ? b.w : b.y, a & 1u);
+}
+
+// Elements (row, env, 0 .. L-1) at once, as a lane that owns all L actions of its env computes
+// them: ceil(L/4) Philox blocks and ceil(L/2) whole pairs (one radius, one cos/sin each); the
+// last level of an odd L takes its pair's cosine alone. Element a is sc_noise_element(.., a).
+template <int L>
+__host__ __device__ __forceinline__ void bg_noise_row(uint32_t k0, uint32_t k1, uint32_t row, uint32_t env, float (&eps)[L]) {
+#pragma unroll
+  for (int g = 0; g < (L + 3) / 4; ++g) {
+    const U4 b = sc_noise_block(k0, k1, row, env, static_cast<uint32_t>(g));
+    const uint32_t w[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int a = 4 * g + 2 * p;
+      if (a + 1 < L) {
+        const NormalPair n = normal_from_words(w[2 * p], w[2 * p + 1]);
+        eps[a] = n.c;
+        eps[a + 1] = n.s;
+      } else if (a < L) {
+        eps[a] = normal_from_words_one(w[2 * p], w[2 * p + 1], false);
+      }
+    }
+  }
 }
 
 }  // namespace scg

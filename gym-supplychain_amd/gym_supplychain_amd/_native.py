@@ -174,6 +174,11 @@ class ScNoiseDraw(ctypes.Structure):
                 ("row0", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class BgNoiseDraw(ctypes.Structure):
+    """scg_bg_noise_draw (include/scgpu.h): the seed and first row of scg_bg_rollout_drawn."""
+    _fields_ = [("seed", ctypes.c_uint64), ("row0", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class BgServerLine(ctypes.Structure):
     """scg_bg_server_line (include/scgpu.h): one slot's 64-byte request line."""
     _fields_ = [("req_seq", ctypes.c_uint32), ("cmd", ctypes.c_int32), ("wpack", ctypes.c_uint32),
@@ -332,6 +337,12 @@ SIGNATURES = {
     "scg_bg_rollout_mlp": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_int32,
                                           ctypes.POINTER(BgMlp), ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "scg_bg_rollout_drawn": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_int32,
+                                            ctypes.POINTER(BgMlp), ctypes.POINTER(BgNoiseDraw), ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.c_void_p]),
+    "scg_bg_noise_fill": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState), ctypes.c_uint64,
+                                         ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_bg_poisson_demand": (ctypes.c_int, [ctypes.POINTER(BgConfig), ctypes.POINTER(BgState),
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "scg_sc_struct_sizes": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)] * 3),

@@ -544,7 +544,7 @@ class BeerGameVecEnv:
 
     def rollout_policy(self, weights, bias=None, n_weeks=None, shift=0, clip=None, return_actions=False,
                        return_obs=False, return_rewards=False, noise=None, std=None, samples_out=None,
-                       return_features=False):
+                       return_features=False, noise_seed=None, noise_row=0):
         """n_weeks weeks in as few launches as possible with every env's action computed on the
         device from its own last observation o (what reset() or the previous step returned):
 
@@ -592,7 +592,15 @@ class BeerGameVecEnv:
         and std (a float or [L], finite, >= 0) go together; samples_out float32 [K, N, L]
         receives u and may be the noise tensor itself; return_features=True returns the int32
         [K, N, L, 4] features each week's action was computed from. The result's `samples` and
-        `features` carry them. With an integer policy these four arguments raise ValueError."""
+        `features` carry them. With an integer policy these four arguments raise ValueError.
+
+        noise_seed, an int in [0, 2^64), instead of noise (never both; std is required, samples_out
+        optional; a pack_local_mlp() policy only): the device draws the noise itself
+        (scg_bg_rollout_drawn), no tensor is read. Week k of the call uses row noise_row + k of
+        draw_noise(noise_seed, ...), whose docstring defines every element; the rows count on
+        across auto-resets inside the call, and a caller who cuts an episode into several calls
+        counts noise_row on (0 <= noise_row, noise_row + n_weeks <= 2^32). The loop is otherwise
+        the one above, bit for bit the call with noise=draw_noise(noise_seed, n_weeks, noise_row)."""
         N, L = self.n_envs, self.levels
         if isinstance(weights, _Packed):
             if bias is not None:
@@ -614,8 +622,13 @@ class BeerGameVecEnv:
             raise ValueError(f"clip=({lo}, {hi}) is empty")
         K = max(int(n_weeks), 0)
         mlp = isinstance(packed, PackedLocalMlp)
-        if not mlp and (noise is not None or std is not None or samples_out is not None or return_features):
-            raise ValueError("noise, std, samples_out and return_features need a pack_local_mlp() policy")
+        drawn = noise_seed is not None
+        if not mlp and (noise is not None or std is not None or samples_out is not None or return_features or drawn):
+            raise ValueError("noise, noise_seed, std, samples_out and return_features need a pack_local_mlp() policy")
+        if drawn and noise is not None:
+            raise ValueError("noise and noise_seed exclude each other")
+        if drawn:
+            noise_seed, noise_row = self._noise_rows(noise_seed, noise_row, K)
         if mlp:
             if shift != 0:
                 raise ValueError(f"a pack_local_mlp() policy takes no shift, got {shift!r}")
@@ -623,8 +636,8 @@ class BeerGameVecEnv:
                 raise ValueError(f"a pack_local_mlp() policy needs clip within +-2**24, got ({lo}, {hi})" +
                                  (": pass clip=(lo, hi)" if clip is None else ""))
             sd = None
-            if noise is not None or std is not None or samples_out is not None:
-                noise, sd, samples_out = self._sampling(K, noise, std, samples_out)
+            if drawn or noise is not None or std is not None or samples_out is not None:
+                noise, sd, samples_out = self._sampling(K, noise, std, samples_out, drawn)
         i32 = dict(dtype=torch.int32, device=self.device)
         res = PolicyRollout(torch.empty(N, dtype=torch.int64, device=self.device),
                             torch.empty((K, N, L), **i32) if return_actions else None,
@@ -637,10 +650,45 @@ class BeerGameVecEnv:
             pol = packed._policy(lo, hi, *bufs)
         else:
             pol = packed._policy(int(shift), lo, hi)
+        head = (ctypes.byref(pol),)
         entry = getattr(nat.lib, packed._entry)
-        nat.check(entry(self._cfg_ref, self._st_ref, int(n_weeks), ctypes.byref(pol), nat.ptr(res.actions),
+        if drawn:
+            head += (ctypes.byref(nat.BgNoiseDraw(noise_seed, noise_row, 0)),)
+            entry = nat.lib.scg_bg_rollout_drawn
+        nat.check(entry(self._cfg_ref, self._st_ref, int(n_weeks), *head, nat.ptr(res.actions),
                         nat.ptr(res.obs), nat.ptr(res.rewards), res.reward_sum.data_ptr(), self._flags, self._stream()))
         return res
+
+    def draw_noise(self, noise_seed, n_weeks, noise_row=0, out=None):
+        """Rows noise_row .. noise_row + n_weeks - 1 of the noise rollout_policy(noise_seed=) draws,
+        float32 [n_weeks, N, L] on the env's device (scg_bg_noise_fill; `out`, a contiguous,
+        16-byte aligned tensor of that kind, is filled and returned): for the learning pass, for
+        chunked calls, for tests. It is the noise SupplyChainVecEnv.draw_noise states, action a
+        being level a: element [k, n, a] is the project's own float32 standard normal (Box-Muller
+        on Philox4x32-10 words), with e = env_offset + n and row = noise_row + k:
+
+            blk      = philox4x32_10(ctr=(e, row, a >> 2, 6), key=(noise_seed & 0xffffffff, noise_seed >> 32))
+            (w1, w2) = (blk[0], blk[1]) if (a >> 1) & 1 == 0 else (blk[2], blk[3])
+            m = (w1 >> 8) + 1;  u = m * 2**-24  in (0, 1]
+            v = w2 >> 8;        theta = 2 * pi * v * 2**-24
+            eps = r * cos(theta) if a is even else r * sin(theta),   r = sqrt(-2 * ln(u))
+
+        r, cos and sin are computed from float32 + - * / sqrt alone, each rounded on its own
+        (csrc/scg_normal.h; tests/noise_ref.py states them in NumPy, bit for bit), within 7.9e-7
+        of the float64 value. A sharded env (env_offset) draws its rows of the unsharded batch,
+        and a SupplyChain env given the same seed draws the same numbers. Up to 8 levels."""
+        N, L = self.n_envs, self.levels
+        if n_weeks is None or isinstance(n_weeks, bool) or not isinstance(n_weeks, (int, np.integer)) or int(n_weeks) < 0:
+            raise ValueError("n_weeks must be a non-negative integer")
+        K = int(n_weeks)
+        noise_seed, noise_row = self._noise_rows(noise_seed, noise_row, K)
+        if out is None:
+            out = torch.empty((K, N, L), dtype=torch.float32, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.device or \
+                tuple(out.shape) != (K, N, L) or not out.is_contiguous() or out.data_ptr() % 16:
+            raise ValueError(f"out must be a contiguous, 16-byte aligned float32 tensor [{K}, {N}, {L}] on {self.device}")
+        nat.check(nat.lib.scg_bg_noise_fill(self._cfg_ref, self._st_ref, noise_seed, noise_row, K, nat.ptr(out), self._stream()))
+        return out
 
     def pack_local_policy(self, weights, bias):
         """Per-env local-information policy parameters in the layout scg_bg_rollout_local reads:
@@ -655,6 +703,7 @@ class BeerGameVecEnv:
         return PackedLocalPolicy(words.t().contiguous(), N, L)
 
     _exact_f32 = SupplyChainVecEnv._exact_f32  # float32 on this env's device, exactly or ValueError
+    _noise_rows = staticmethod(SupplyChainVecEnv._noise_rows)  # the checked (seed, first row) of a drawn call
 
     def pack_local_mlp(self, w1, b1, w2, b2):
         """One-hidden-layer ReLU policy parameters over the local features in the layout
@@ -682,10 +731,14 @@ class BeerGameVecEnv:
         b2 = self._exact_f32("b2", b2, ((L,),))
         return PackedLocalMlp(pack_mlp_words(w1, b1, w2, b2), N, L, H)
 
-    def _sampling(self, K, noise, std, samples_out):
-        """The checked (noise, std on the device, samples_out) of a sampled rollout_policy call."""
+    def _sampling(self, K, noise, std, samples_out, drawn=False):
+        """The checked (noise, std on the device, samples_out) of a sampled rollout_policy call
+        (drawn: the device draws the noise, and none is passed)."""
         N, L = self.n_envs, self.levels
-        if noise is None or std is None:
+        if drawn:
+            if std is None:
+                raise ValueError("noise_seed needs std")
+        elif noise is None or std is None:
             raise ValueError("noise and std go together" if noise is not None or std is not None else
                              "samples_out needs noise and std")
         for name, x in (("noise", noise), ("samples_out", samples_out)):

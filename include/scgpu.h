@@ -59,7 +59,9 @@ extern "C" {
  *   policy in float32 over the local features, deterministic or sampled from the caller's
  *   noise), an added entry point; also scg_sc_rollout_drawn, scg_sc_noise_fill and the testing
  *   hook scg_noise_from_words (scg_sc_noise_draw: the sampled SupplyChain closed loop with
- *   its noise drawn on the device from a seed and a row counter), added entry points. */
+ *   its noise drawn on the device from a seed and a row counter), added entry points; also
+ *   scg_bg_rollout_drawn and scg_bg_noise_fill (scg_bg_noise_draw: the sampled BeerGame MLP
+ *   loop with the same noise drawn on the device), added entry points. */
 #define SCG_ABI_VERSION 9
 
 #if defined(__GNUC__)
@@ -530,6 +532,40 @@ SCG_API int scg_bg_rollout_mlp(const scg_bg_config* cfg, scg_bg_state* st, int32
                                uint32_t flags, void* stream);
 
 /*
+ * scg_bg_rollout_mlp's sampled loop with the noise drawn on the device: noise[k][n][a] is not read
+ * from memory but computed by the lane that owns the env, at the top of the week. It is the noise
+ * of the SupplyChain closed loop (scg_sc_noise_draw below states the element; csrc/scg_normal.h is
+ * the one definition, tests/noise_ref.py its NumPy statement): stream SCG_STREAM_SC_NOISE serves
+ * both env families, a BeerGame action a is level a, and a BeerGame and a SupplyChain env given the
+ * same seed draw the same numbers. The eps of week j of the call is element (row0 + j,
+ * env_offset + n, a); j counts on across the launches a call is cut into and across auto-resets
+ * inside the call, so a sharded batch draws what the unsharded one draws and a caller who cuts an
+ * episode into several calls passes each its own row0.
+ *   std, samples_out, features_out, params, hidden and the clamp are `policy`'s; policy->noise
+ *   must be NULL. seed is the noise's own (not the state's); row0 the global row of the call's
+ *   first week.
+ * Contract, flags, the launch cut, the n_weeks == 0 path and the error codes are
+ * scg_bg_rollout_mlp's. Checked before any HIP call, st left untouched: SCG_ERR_INVALID for a NULL
+ * draw, for reserved != 0, for a non-NULL policy->noise, for a NULL policy->std with n_weeks > 0,
+ * for row0 + n_weeks > 2^32, and for everything scg_bg_rollout_mlp refuses.
+ */
+typedef struct scg_bg_noise_draw {
+  uint64_t seed;
+  uint32_t row0;
+  uint32_t reserved;   /* 0 */
+} scg_bg_noise_draw;   /* 16 bytes */
+
+SCG_API int scg_bg_rollout_drawn(const scg_bg_config* cfg, scg_bg_state* st, int32_t n_weeks, const scg_bg_mlp* policy,
+                                 const scg_bg_noise_draw* draw, int32_t* actions_out, int32_t* obs, int32_t* rewards,
+                                 int64_t* reward_sum, uint32_t flags, void* stream);
+
+/* Rows row0 .. row0 + n_rows - 1 of that noise for the state's envs, into out DEVICE float32
+ * [n_rows][N][L] (levels <= SCG_BG_POLICY_MAX_LEVELS). SCG_ERR_INVALID for a NULL out with
+ * n_rows > 0, n_rows < 0 or row0 + n_rows > 2^32. */
+SCG_API int scg_bg_noise_fill(const scg_bg_config* cfg, const scg_bg_state* st, uint64_t seed, uint32_t row0,
+                              int32_t n_rows, float* out, void* stream);
+
+/*
  * Device-side Philox draws for tests and benchmarks (no host round trip):
  *  scg_bg_poisson_demand: out DEVICE int32 [T][N], the demand scg_bg_step draws
  *    for episode `episode` in SCG_DEMAND_POISSON mode.
@@ -576,6 +612,8 @@ SCG_API int scg_uniform_ints(uint64_t seed, int64_t env_offset, int64_t n_envs, 
 #define SCG_SC_LAYOUT_ENV_MAJOR 1   /* stock [N][NP], heaps [N][NP][H], sizes [N][NP]          */
 #define SCG_STREAM_SC_DEMAND 2u
 #define SCG_STREAM_SC_LEADTIME 3u
+/* Stream 6 serves both env families (scg_sc_noise_draw, scg_bg_noise_draw): a BeerGame and a
+ * SupplyChain env given the same seed draw the same numbers. */
 #define SCG_STREAM_SC_NOISE 6u /* the exploration noise a closed loop draws itself (scg_sc_noise_draw) */
 
 /* One chain node (SC_Node :106-206 after define_destinations), in nodes_info order. */
